@@ -16,10 +16,20 @@ Workloads (--workload):
   --forward-only   BASELINE.json configs[1]: eval-mode forward of the chosen workload (BatchNorm folded).
 The convolution trunk runs in bf16 on MFMA, heads in fp32.  The whole step is captured once in a HIP graph and replayed.
 
-Prints ONE JSON line (rank 0): images/sec over all GPUs, the roofline entry of the dominant kernel family (durations
-measured with HIP events on the launch stream in an instrumented pass of the same step), a CPU baseline of the same
-step timed with the oracle on the host cores, the step time without the optimizer, and the end-to-end key-point error in
-pixels against the reference's fixture.
+Prints ONE JSON line (rank 0): images/sec over all GPUs and the milliseconds of one timed step (`ms_per_step`).  A plain run
+does only that: set up, warm up, time --steps steps, write the outputs of the last step (--dump-outputs DIR), print the line.
+
+--full adds everything else, each part a run of its own after the timed steps: the roofline entry of the dominant kernel
+family and the per-family kernel times (durations measured with HIP events on the launch stream in an instrumented pass of
+the same step), the step time without the optimizer, the end-to-end key-point error in pixels against the reference's
+fixture, the secondary workloads and precisions (hrnet_step, forward_only, fp32_step, ... in child processes) and a CPU
+baseline of the same step timed with the oracle on the host cores.
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32, or float64 where the
+tensor is): the forward outputs, the loss and, for a training step, the parameters after the update and their gradients.
+An array of more than DUMP_SAMPLE elements is a fixed, seeded sample of DUMP_SAMPLE of them (the parameters and gradients:
+the same positions of the flat concatenation in model.parameters() order).  The inputs are seeded: the same arguments give
+the same inputs in every run.
 """
 import argparse
 import json
@@ -327,6 +337,45 @@ def keypoint_px_error(dev, dtypes):
     return out
 
 
+DUMP_SAMPLE = 1 << 20      # elements per dumped array at most (a seeded sample beyond): 4-8 MB each, far below 64 MB in all
+OUTPUT_NAMES = ("pose", "rot", "trans", "root_uv", "depth", "uvd", "xyz_int", "xyz_fk")     # RootNetwithRegInt.forward
+
+
+def _host(t):
+    return t.detach().to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+
+
+def _sample(tensors, seed):
+    """The flat concatenation of `tensors` or, beyond DUMP_SAMPLE elements, the same seeded DUMP_SAMPLE positions of it, in
+    order.  tensors: [(tensor, numel)]; a None tensor stands for numel zeros (a parameter without a gradient)."""
+    total = sum(n for _, n in tensors)
+    idx = np.arange(total) if total <= DUMP_SAMPLE else \
+        np.sort(np.random.Generator(np.random.PCG64(seed)).choice(total, DUMP_SAMPLE, replace=False))
+    parts, off = [], 0
+    for t, n in tensors:
+        lo, hi = np.searchsorted(idx, [off, off + n])
+        if hi > lo:
+            parts.append(np.zeros(hi - lo, np.float32) if t is None else
+                         _host(t.detach().reshape(-1)[torch.from_numpy(idx[lo:hi] - off).to(t.device)]))
+        off += n
+    return np.concatenate(parts) if parts else np.zeros(0, np.float32)
+
+
+def dump_outputs(path, holder, params):
+    """--dump-outputs: what the last timed step computed, as the step's caller receives it - the forward outputs, the loss and,
+    for a training step (params not None), the parameters after the update and this step's gradients."""
+    os.makedirs(path, exist_ok=True)
+    outs = holder["outputs"]
+    names = OUTPUT_NAMES if len(outs) == len(OUTPUT_NAMES) else ("depth",)      # the full network / DepthNet
+    arrays = {n: _host(t) if t.numel() <= DUMP_SAMPLE else _sample([(t, t.numel())], 1) for n, t in zip(names, outs)}
+    arrays["loss"] = _host(holder["loss"])
+    if params is not None:
+        arrays["params"] = _sample([(p, p.numel()) for p in params], 2)
+        arrays["grads"] = _sample([(p.grad, p.numel()) for p in params], 2)
+    for n, v in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -347,9 +396,16 @@ def main():
     ap.add_argument("--workload", default="full", choices=["full", "hrnet"],
                     help="full: the full network (headline, BASELINE.json configs[2]); hrnet: one HRNet-W32 (DepthNet), the metric's literal workload")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the two secondary measurements of the default invocation (hrnet_step, forward_only)")
-    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # a secondary measurement of the default invocation
+                    help="--full: skip the secondary measurements in child processes (hrnet_step, forward_only, fp32_step, ...)")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # a secondary measurement of a --full invocation
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: instrumented per-kernel pass + roofline, step without the optimizer, key-point "
+                         "pixel error, the secondary workloads / precisions (unless --no-extra) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (see the module docstring)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ and not a.cpu_baseline_only:
         self_launch(a, sys.argv[1:])
 
@@ -394,6 +450,13 @@ def main():
     K = d["K"]
     kv = compute_k_values(K[:, 0, 0], K[:, 1, 1], d["bbox"])
     loss_holder = {}
+
+    def keep(out):
+        """The forward's outputs as the caller of the step receives them (detached views; a captured graph rewrites them on every
+        replay): what --dump-outputs writes after the timed steps."""
+        loss_holder["outputs"] = tuple(t.detach() for t in (out if isinstance(out, tuple) else (out,)))
+        return out
+
     h2d = os.environ.get("HRP_BENCH_H2D")
     if h2d in ("u8", "u8res"):     # the dataset's bytes: the model's input kernel divides by 255 (SURVEY 8 f-1)
         for k in ("x_reg", "x_root"):
@@ -402,7 +465,7 @@ def main():
         gt_depth = d["t"][:, 2:3].contiguous()
 
         def forward():
-            return model(d["x_root"], kv)
+            return keep(model(d["x_root"], kv))
 
         def fwd_bwd():
             loss = depth_l1_loss(forward(), gt_depth)   # scripts/train_depthnet.py:231-250 (one launch, analytic gradient)
@@ -417,7 +480,7 @@ def main():
                       mask=torch.ones(B, 7, device=dev))
 
         def forward():
-            return model(d["x_reg"], d["x_root"], kv, K)
+            return keep(model(d["x_reg"], d["x_root"], kv, K))
 
         def fwd_bwd():
             loss, _ = full_loss(forward(), gt, K)
@@ -603,10 +666,12 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         dt = tt.item()
     final_loss = float(loss_holder["loss"].item())
+    if a.dump_outputs and rank == 0:     # before anything else runs the step again
+        dump_outputs(a.dump_outputs, loss_holder, None if fwd_only else params)
 
     # the same step without clip + Adam (SURVEY 8d C3 "Adam excluded and included: report both"), one GPU only
     ms_no_opt = None
-    if world == 1 and use_graph and not fwd_only and not h2d and not os.environ.get("HRP_BENCH_TWO_GRAPHS") and not force_world1():
+    if a.full and world == 1 and use_graph and not fwd_only and not h2d and not os.environ.get("HRP_BENCH_TWO_GRAPHS") and not force_world1():
         gno = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gno):
             fwd_bwd()
@@ -623,6 +688,47 @@ def main():
         return
     ms_per_step = dt / a.steps * 1e3
     value = B * world * a.steps / dt
+
+    from hrpe_amd import plan as plan_mod
+    # (fp32x3: three bf16 MFMAs per product - its roof is a third of the bf16 matrix peak)
+    peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else (PEAK_F32_TFLOPS if a.dtype == "fp32" else PEAK_BF16_TFLOPS / 3.0)
+    gf_img = FWD_GFLOP_PER_IMAGE["depthnet" if hrnet else "full"] * (1 if fwd_only else 3)
+    step_tflops = gf_img * 1e9 * B * world / (ms_per_step * 1e-3) / 1e12 / world     # per GPU
+    passes = 1 if hrnet else 2
+    net = ("one HRNet-W32 (RootNet('hrnet32') = DepthNet, the metric's literal workload)" if hrnet else
+           f"full network ({'HRNet-W32' if REG_BACKBONE.startswith('hrnet') else REG_BACKBONE + ' + deconv head'} reg backbone + "
+           "HRNet-W32 DepthNet + heads + FK loss)")
+    what = (f"{net} eval forward (BatchNorm folded), BASELINE.json configs[1]" if fwd_only else
+            f"{net} fwd+loss+bwd+clip+Adam" + ("" if hrnet else ", BASELINE.json configs[2]"))
+    clip = 1 if hrnet else 5
+    # which collective library carried the gradients: "rccl_ranks" is only printed when it was RCCL ("nccl" on ROCm) - a gloo
+    # run (two ranks on one GPU, a development configuration) must not read as an RCCL measurement
+    import torch.distributed as _dist
+    backend = _dist.get_backend() if (_dist.is_available() and _dist.is_initialized()) else "single-process"
+    out = {
+        "metric": "images/sec/GPU fwd+bwd HRNet-W32 256x256 bs=64; 1/2/4/8-GPU scaling",
+        "value": round(value, 2), "value_per_gpu": round(value / world, 2), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": what,
+                   "global_batch": B * world, "per_gpu_batch": B, "image": "3x256x256",
+                   "hrnet_w32_passes_per_image": passes, "parallelism": f"dp{world}", "backend": backend,
+                   **({"rccl_ranks": world} if backend in ("nccl", "single-process") else {}), "hip_graph": use_graph,
+                   "plan_mode": plan_mod.PLAN_MODE, "p_dropout": 0.0 if (hrnet or fwd_only) else a.p_dropout,
+                   "inputs": {None: "resident in HBM", "u8": "uint8 images from pinned host memory every step (PCIe-inclusive)",
+                              "f32": "fp32 images from pinned host memory every step (PCIe-inclusive)",
+                              "u8res": "uint8 images resident in HBM"}[h2d],
+                   "optimizer": None if fwd_only else (f"clip_grad_norm_({clip})+torch.optim.Adam(fused)" if a.torch_optim else
+                                                      f"hrpe_amd.optim.FusedClipAdam (clip {clip} + Adam, lr 1e-4)")},
+        "hrnet_w32_passes_per_sec": round(passes * value, 2),
+        "step_model_tflops": round(step_tflops, 2),
+        "step_frac_of_mfma_peak": round(step_tflops / peak, 4),
+        "loss": final_loss,
+        **info,
+    }
+    if not a.full:      # a plain run: the headline line and nothing else
+        print(json.dumps(out))
+        return
 
     # ---- instrumented pass: HIP events around every C-ABI launch on the launch stream --------------
     records, records_shape = [], []
@@ -657,7 +763,6 @@ def main():
             records_shape.append((fam, fl, e0, e1, shape_key(name, args)))
 
     # lanes (concurrent graph branches) are folded onto one stream here: a kernel's duration is its own
-    from hrpe_amd import plan as plan_mod
     if not fwd_only:
         model.disable_split_backward()      # (N > 1: the timed step ran the backward in two graphs)
     plan_mod.SERIAL_LANES = True
@@ -690,8 +795,6 @@ def main():
     kernels = {n: {"launches": v[0], "ms": round(v[1], 3), "tflops": round(v[2] / (v[1] * 1e-3) / 1e12, 1) if v[2] else None}
                for n, v in sorted(fam.items(), key=lambda kv: -kv[1][1])}
     dom = max(fam.items(), key=lambda kv: kv[1][1])
-    # (fp32x3: three bf16 MFMAs per product - its roof is a third of the bf16 matrix peak)
-    peak = PEAK_BF16_TFLOPS if a.dtype == "bf16" else (PEAK_F32_TFLOPS if a.dtype == "fp32" else PEAK_BF16_TFLOPS / 3.0)
     ach_tf = dom[1][2] / (dom[1][1] * 1e-3) / 1e12 if dom[1][2] else 0.0
     ach_gb = dom[1][3] / (dom[1][1] * 1e-3) / 1e9 if dom[1][3] else 0.0
     # which roof binds the family: its arithmetic intensity against the ridge point peak_flops / peak_bytes
@@ -761,43 +864,9 @@ def main():
                 "mfma_tflops": round(ach_tf, 2), "mfma_frac": round(ach_tf / peak, 4)}
     if profiled:
         roofline["profiled"] = profiled
-    gf_img = FWD_GFLOP_PER_IMAGE["depthnet" if hrnet else "full"] * (1 if fwd_only else 3)
-    step_tflops = gf_img * 1e9 * B * world / (ms_per_step * 1e-3) / 1e12 / world     # per GPU
-    passes = 1 if hrnet else 2
-    net = ("one HRNet-W32 (RootNet('hrnet32') = DepthNet, the metric's literal workload)" if hrnet else
-           f"full network ({'HRNet-W32' if REG_BACKBONE.startswith('hrnet') else REG_BACKBONE + ' + deconv head'} reg backbone + "
-           "HRNet-W32 DepthNet + heads + FK loss)")
-    what = (f"{net} eval forward (BatchNorm folded), BASELINE.json configs[1]" if fwd_only else
-            f"{net} fwd+loss+bwd+clip+Adam" + ("" if hrnet else ", BASELINE.json configs[2]"))
-    clip = 1 if hrnet else 5
-    # which collective library carried the gradients: "rccl_ranks" is only printed when it was RCCL ("nccl" on ROCm) - a gloo
-    # run (two ranks on one GPU, a development configuration) must not read as an RCCL measurement
-    import torch.distributed as _dist
-    backend = _dist.get_backend() if (_dist.is_available() and _dist.is_initialized()) else "single-process"
-    out = {
-        "metric": "images/sec/GPU fwd+bwd HRNet-W32 256x256 bs=64; 1/2/4/8-GPU scaling",
-        "value": round(value, 2), "value_per_gpu": round(value / world, 2), "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": what,
-                   "global_batch": B * world, "per_gpu_batch": B, "image": "3x256x256",
-                   "hrnet_w32_passes_per_image": passes, "parallelism": f"dp{world}", "backend": backend,
-                   **({"rccl_ranks": world} if backend in ("nccl", "single-process") else {}), "hip_graph": use_graph,
-                   "plan_mode": plan_mod.PLAN_MODE, "p_dropout": 0.0 if (hrnet or fwd_only) else a.p_dropout,
-                   "inputs": {None: "resident in HBM", "u8": "uint8 images from pinned host memory every step (PCIe-inclusive)",
-                              "f32": "fp32 images from pinned host memory every step (PCIe-inclusive)",
-                              "u8res": "uint8 images resident in HBM"}[h2d],
-                   "optimizer": None if fwd_only else (f"clip_grad_norm_({clip})+torch.optim.Adam(fused)" if a.torch_optim else
-                                                      f"hrpe_amd.optim.FusedClipAdam (clip {clip} + Adam, lr 1e-4)")},
-        "hrnet_w32_passes_per_sec": round(passes * value, 2),
-        "ms_per_step_without_optimizer": round(ms_no_opt, 3) if ms_no_opt is not None else None,
-        "step_model_tflops": round(step_tflops, 2),
-        "step_frac_of_mfma_peak": round(step_tflops / peak, 4),
-        "roofline": roofline,
-        "kernels": kernels,
-        "loss": final_loss,
-        **info,
-    }
+    out["ms_per_step_without_optimizer"] = round(ms_no_opt, 3) if ms_no_opt is not None else None
+    out["roofline"] = roofline
+    out["kernels"] = kernels
     if a.child:     # a secondary measurement: the parent embeds this line
         out["roofline"].pop("traffic", None)
         out["roofline"].pop("traffic_source", None)
@@ -814,7 +883,7 @@ def main():
         met = {"bf16": bool(max(mp["bf16_by_keypoint"]) < 0.5), "fp32": bool(mp.get("fp32_vs_fp64", 1.0) < 0.5),
                "fp32x3": bool(mp.get("fp32x3_vs_fp64", 1.0) < 0.5)}
         out["px_bar_met"] = {"bar_px": 0.5, **met, "benchmarked_dtype": a.dtype, "benchmarked_dtype_meets_bar": met.get(a.dtype)}
-    # The default invocation also times the metric's literal workload (ONE HRNet-W32 = DepthNet, forward + L1 + backward +
+    # A --full run also times the metric's literal workload (ONE HRNet-W32 = DepthNet, forward + L1 + backward +
     # clip + Adam) and BASELINE.json configs[1] (the full network's eval forward, BatchNorm folded), 10 steps each, in fresh
     # processes (one training plan per process: a second plan next to the first runs ~16 % slower), while this
     # process idles on the GPU.  Each carries its own roofline entry; `value` above stays the headline.
@@ -830,7 +899,7 @@ def main():
                            ("forward_only_fp32x3", ["--forward-only", "--dtype", "fp32x3"])):
             r = None
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--no-cpu-baseline", "--steps", "10",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--child", "--no-cpu-baseline", "--steps", "10",
                                     "--warmup", "3"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240)
                 c = json.loads(r.stdout.strip().splitlines()[-1])
                 out[key] = {k: c[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "step_model_tflops",

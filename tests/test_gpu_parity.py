@@ -182,13 +182,22 @@ def test_full_bf16_against_reference_fixtures():
     _bf16_train_step(m)
 
 
-def test_full_train_step_b64_against_oracle_and_bf16():
+@pytest.fixture
+def host_threads():
+    """Up to 16 host threads for the oracle of one test, then the count before it again: the tests that run later in the
+    session (tests/test_oracle_golden.py) compare with fixtures the reference summed on 8 threads."""
+    saved = torch.get_num_threads()
+    torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)))))
+    yield
+    torch.set_num_threads(saved)
+
+
+def test_full_train_step_b64_against_oracle_and_bf16(host_threads):
     """One fp32 training step at B = 64 against the CPU oracle on the host, then bf16 against fp32 HIP on the same batch."""
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from oracle import fk as ofk, heads as oheads
     from hrpe_amd.lib.core.function import full_loss
     B = 64
-    torch.set_num_threads(max(1, min(16, len(os.sched_getaffinity(0)))))
     m = build_full().train()
     sd = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
     for k, v in sd.items():

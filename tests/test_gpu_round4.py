@@ -122,14 +122,14 @@ def _bf16_px_by_keypoint():
 
 def test_bf16_keypoint_0_documents_known_bf16_defect():
     """The benchmarked precision, in pixels.  This test DOCUMENTS A KNOWN DEFECT of the bf16 mode against the north star's pixel bar
-    (VERDICT r4 weak #1, item 4c); it does not claim the bar is met: bench.py prints "px_bar_met": {"bf16": false, "fp32": true}.
+    (VERDICT r4 weak #1, item 4c); it does not claim the bar is met: bench.py --full prints "px_bar_met": {"bf16": false, "fp32": true}.
     Six of the seven key-points of the fixture stay below 0.5 px (gated).  Key-point 0 sits 0.13 m in front of the camera (f = 800 px:
     1 mm of root depth is 3 px) and is off by 4.5 px in bf16 (gated at 5.5 so that it cannot get worse unnoticed).  What round 5
     measured about closing it: the DepthNet's head in fp32 0.92 px (+6.6 ms), the WHOLE DepthNet in fp32
     (HRP_DEPTHNET_FP32_FROM=1) still 2.4 px at 92 ms per step - the rest is the bf16 regression trunk's pose / rotation error seen
     from 0.13 m; a CPU emulation of the storage precisions (tools/emulate_bf16_modes.py) puts an fp32 residual stream at 0.9 px and
     bf16 WEIGHTS alone (every activation fp32) at 2.0 px.  No mode with bf16 operands meets 0.5 px on this key-point; the mode that
-    does is fp32 (0.0011 px, tests/test_gpu_round3.py), whose step bench.py times as `fp32_step` (133 ms, 0.43 of the fp32 matrix peak)."""
+    does is fp32 (0.0011 px, tests/test_gpu_round3.py), whose step bench.py --full times as `fp32_step` (133 ms, 0.43 of the fp32 matrix peak)."""
     from hrpe_amd.lib.models.backbones import HRnet
     by_kp, r = _bf16_px_by_keypoint()
     print("\nbf16 px error by key-point:", by_kp)

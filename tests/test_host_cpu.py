@@ -688,30 +688,42 @@ def test_resnet_full_net_state_dict_keys():
 def test_bench_self_launch_spawns_ranks_before_any_gpu_call(monkeypatch):
     """`python bench.py --gpus N` outside torch.distributed.run: the parent starts N ranks through
     `python -m torch.distributed.run` (127.0.0.1 rendezvous) without having initialised HIP itself, and a rank whose
-    WORLD_SIZE disagrees with --gpus refuses to print a mislabelled line."""
+    WORLD_SIZE disagrees with --gpus refuses to print a mislabelled line.  The parent runs in a fresh interpreter: in this one
+    an earlier GPU test of the session may have initialised HIP already."""
     import importlib
-    import subprocess as sp
-    import torch
-    sys.path.insert(0, ROOT)
-    bench = importlib.import_module("bench")
-    seen = {}
-
-    class R:
-        returncode = 0
-
-    def fake_run(cmd, env=None, **kw):
-        seen["cmd"], seen["env"], seen["cuda_init"] = cmd, env, torch.cuda.is_initialized()
-        return R()
-    monkeypatch.setattr(sp, "run", fake_run)
-    monkeypatch.delenv("WORLD_SIZE", raising=False)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"])
-    with pytest.raises(SystemExit) as e:
-        bench.main()
-    assert e.value.code == 0
+    import json
+    parent = r"""
+import json, subprocess as sp, sys
+sys.path.insert(0, sys.argv[1])
+import torch
+import bench
+seen = {}
+class R:
+    returncode = 0
+def fake_run(cmd, env=None, **kw):
+    seen.update(cmd=cmd, env=env, cuda_init=torch.cuda.is_initialized())
+    return R()
+sp.run = fake_run
+sys.argv = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"]
+try:
+    bench.main()
+except SystemExit as e:
+    seen["code"] = e.code
+print(json.dumps(seen))
+"""
+    env = {k: v for k, v in os.environ.items() if k != "WORLD_SIZE"}
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", parent, ROOT], env=env,
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    seen = json.loads(r.stdout.strip().splitlines()[-1])
+    assert seen["code"] == 0
     cmd = seen["cmd"]
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=2" in cmd and "127.0.0.1" in cmd
     assert cmd[cmd.index("--master-port") + 1].isdigit() and cmd[-6:] == ["--gpus", "2", "--steps", "3", "--warmup", "1"]
     assert seen["cuda_init"] is False and seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"])
     # inside a launcher whose world size disagrees with --gpus: no line
     monkeypatch.setenv("WORLD_SIZE", "1")
     monkeypatch.setenv("RANK", "0")
@@ -719,6 +731,38 @@ def test_bench_self_launch_spawns_ranks_before_any_gpu_call(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "mislabelled" in str(e.value)
+
+
+def test_bench_dump_outputs_writes_seeded_samples(tmp_path):
+    """bench.py --dump-outputs: the forward outputs as float32 (float64 stays float64) with their shapes, the loss, and a fixed
+    seeded sample of the flat parameters / gradients at the same positions (a parameter without a gradient counts as zeros);
+    two dumps of the same tensors are identical and stay far below 64 MB."""
+    import importlib
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(0)
+    params = [torch.nn.Parameter(torch.randn(n, generator=g)) for n in (700_000, 3, 900_000, 11)]
+    for p in params[:-1]:
+        p.grad = torch.randn(p.shape, generator=g)
+    outs = tuple(torch.randn(4, k, generator=g) for k in (8, 6, 3, 2, 1)) + \
+        (torch.randn(4, 7, 3, generator=g).bfloat16(), torch.randn(4, 7, 3, generator=g), torch.randn(4, 7, 3, generator=g).double())
+    holder = {"outputs": outs, "loss": torch.tensor(0.25)}
+    bench.dump_outputs(str(tmp_path / "a"), holder, params)
+    bench.dump_outputs(str(tmp_path / "b"), holder, params)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n in bench.OUTPUT_NAMES + ("loss", "params", "grads"))
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == (np.float64 if f == "xyz_fk.npy" else np.float32) and np.array_equal(a, b), f
+    assert np.load(tmp_path / "a" / "uvd.npy").shape == (4, 7, 3) and float(np.load(tmp_path / "a" / "loss.npy")) == 0.25
+    total = sum(p.numel() for p in params)
+    idx = np.sort(np.random.Generator(np.random.PCG64(2)).choice(total, bench.DUMP_SAMPLE, replace=False))
+    flat = torch.cat([p.detach().reshape(-1) for p in params]).numpy()
+    grads = torch.cat([p.grad.reshape(-1) if p.grad is not None else torch.zeros(p.numel()) for p in params]).numpy()
+    assert np.array_equal(np.load(tmp_path / "a" / "params.npy"), flat[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "grads.npy"), grads[idx])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
 
 
 def test_silhouette_oracle_known_answers_and_obj_loader(tmp_path):

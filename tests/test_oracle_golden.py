@@ -25,6 +25,17 @@ def check_summary(t, g, key, rtol, atol):
     np.testing.assert_allclose(f[idx].float().numpy(), val, rtol=rtol, atol=atol)
 
 
+def check_grad(sd, g, name, rtol, atol):
+    """One parameter's gradient against the reference's summary.  A gradient the reference has at rounding-noise level - mean |g|
+    below 1e-6 of the fixture's largest: a bias in front of a training-mode BatchNorm, analytically zero - is noise whose value
+    follows the CPU's summation order; it must be noise at that level here too, not the reference's noise."""
+    floor = 1e-6 * max(float(g[k][1]) for k in g.files if k.startswith("grad:") and k.endswith(":summary"))
+    if float(g[f"grad:{name}:summary"][1]) < floor:
+        assert float(sd[name].grad.abs().max()) < floor, name
+    else:
+        check_summary(sd[name].grad, g, f"grad:{name}:", rtol=rtol, atol=atol)
+
+
 def hrnet_shapes(prefix="", hm=True, feat=True, depth_dim=64, num_joints=7):
     """State-dict key -> shape of the reference HRNet-W32 (built from the product module tree)."""
     from hrpe_amd.lib.models.backbones.HRnet import get_hrnet
@@ -153,8 +164,7 @@ def test_depthnet_golden():
     np.testing.assert_allclose(loss.item(), g["loss"], rtol=1e-5)
     for key in g.files:
         if key.startswith("grad:") and key.endswith(":val"):
-            name = key.split(":")[1]
-            check_summary(sd[name].grad, g, f"grad:{name}:", rtol=2e-3, atol=1e-9)
+            check_grad(sd, g, key.split(":")[1], rtol=2e-3, atol=1e-9)
         if key.startswith("buf:"):
             np.testing.assert_allclose(sd[key[4:]][:64].detach().numpy(), g[key], rtol=1e-5, atol=1e-7)
 
@@ -186,12 +196,13 @@ def test_depthnet_variants_golden():
     pred = heads.rootnet_forward(sd, x, kv, training=True, use_offset=True, add_fc=True) / 1000.0
     loss = torch.nn.functional.l1_loss(pred, torch.tensor(g["gt_depth"]))
     loss.backward()
-    np.testing.assert_allclose(pred.detach().numpy(), g["depth_train"], rtol=1e-5)
+    # (B = 8 through four training-mode BatchNorm1d layers: other CPU families sum in another order - 2.5e-5 of the prediction,
+    # 3.3e-3 / 1.5e-7 of the gradients measured between two of them)
+    np.testing.assert_allclose(pred.detach().numpy(), g["depth_train"], rtol=5e-5)
     np.testing.assert_allclose(loss.item(), g["loss"], rtol=1e-5)
     for key in g.files:
         if key.startswith("grad:") and key.endswith(":val"):
-            name = key.split(":")[1]
-            check_summary(sd[name].grad, g, f"grad:{name}:", rtol=2e-3, atol=1e-9)
+            check_grad(sd, g, key.split(":")[1], rtol=5e-3, atol=2e-7)
         if key.startswith("buf:"):
             np.testing.assert_allclose(sd[key[4:]][:64].detach().numpy(), g[key], rtol=1e-5, atol=1e-7)
 

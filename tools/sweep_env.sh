@@ -2,7 +2,7 @@
 # development aid: bench.py under a list of environment settings (one per line on stdin: "VAR=val VAR2=val"), prints
 # ms_per_step and the kernel-time of the element-wise / conv / wgrad families
 while read -r line; do
-  out=$(env $line timeout 200 python bench.py --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | tail -1)
+  out=$(env $line timeout 200 python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline 2>/dev/null | tail -1)
   python - "$line" <<PY "$out"
 import json, sys
 try:
