@@ -286,6 +286,8 @@ PROTOTYPES = {
     "hrp_linear_wgrad_batch": [_P, _I, _P],
     "hrp_project_fwd": [_P, _P, _I, _I, _P, _P],
     "hrp_project_bwd": [_P, _P, _P, _I, _I, _P, _P],
+    "hrp_pnp_solve": [_P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P],
+    "hrp_pnp_bwd": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
 }
 
 _lib = None

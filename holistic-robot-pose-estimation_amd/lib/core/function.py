@@ -32,9 +32,9 @@ def prepare_batch(input_batch, robot, device, reference_keypoint_id=3, use_origi
 
     Returns dict(reg_images, root_images, root_K, other_K, k_values, gt = dict(pose, rot, trans, root_rot,
     root_trans, root_depth, root_uv, kp3d, kp2d, mask)); ``gt`` feeds ``full_loss``.  `synthetic=False` (real
-    datasets) needs the reference's BPnP solve on the CPU (function.py:66-74), which is outside this build."""
-    if not synthetic:
-        raise NotImplementedError("BPnP ground-truth rotation for real datasets (function.py:66-74) is not part of this build")
+    datasets, function.py:66-74): the ground-truth rotation is the PnP solution (lib/utils/BPnP.py BPnP_m3d, one launch for
+    the batch) of the annotated ``keypoints_2d_original`` against the FK key-points of the ground-truth joint angles under
+    ``K_original[0]``; ``root_rot`` follows from it, ``trans`` stays TCO's."""
 
     def dev(t, dtype=torch.float32):
         return torch.as_tensor(t).to(device=device, dtype=dtype, non_blocking=True)
@@ -53,6 +53,12 @@ def prepare_batch(input_batch, robot, device, reference_keypoint_id=3, use_origi
     pose = torch.stack([dev(jp[k]) for k in JOINT_NAMES[robot.robot_type]], dim=1)        # :51
     to_rot = rotmat_to_quat if rotation_dim == 4 else rotmat_to_rot6d                        # :60-65
     rot, trans = to_rot(TCO[:, :3, :3]), TCO[:, :3, 3].contiguous()                          # :53-54
+    if not synthetic:                                                                      # :66-74
+        from hrpe_amd.lib.utils.BPnP import BPnP_m3d
+        from hrpe_amd.lib.utils.geometries import angle_axis_to_rotation_matrix
+        world_3d_pts = robot.get_keypoints_only_fk(pose)
+        P_6d = BPnP_m3d.apply(dev(input_batch["keypoints_2d_original"]), world_3d_pts, dev(input_batch["K_original"])[0])
+        rot = to_rot(angle_axis_to_rotation_matrix(P_6d[:, 0:3])[:, :3, :3]).float()
     kp3d, kp2d = dev(other["keypoints_3d"]), dev(other["keypoints_2d"])
     if reference_keypoint_id == 0:                                                         # :76-78
         root_trans, root_rot = trans, rot

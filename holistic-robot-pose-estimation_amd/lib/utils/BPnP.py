@@ -1,0 +1,153 @@
+"""Back-propagatable PnP with the reference's names (lib/utils/BPnP.py), on the GPU.
+
+``BPnP`` (shared pts3d [n,3]), ``BPnP_m3d`` (pts3d [B,n,3]) and ``BPnP_fast`` take ``(pts2d [B,n,2], pts3d, K [3,3], ini_pose=None)``
+and return P_6d [B,6] (angle-axis with |w| <= pi, then translation) in fp32 on pts2d's device.  K may also be [B,3,3].
+
+Forward (csrc/pnp.hip hrp_pnp_solve): one launch for the batch.  EPnP gives the start (the reference's cv2.solvePnP SOLVEPNP_EPNP,
+BPnP.py:36, 140), or ``ini_pose`` does (:142-145); Levenberg-Marquardt on the reprojection error then refines it (SOLVEPNP_ITERATIVE
+with useExtrinsicGuess, :41, 146).  ``BPnP_fast`` starts from the same EPnP solution: the reference's RANSAC start
+(cv2.solvePnPRansac, :266) is not built.
+Backward (hrp_pnp_bwd): the reference's formula, -g^T J_fy^-1 J_f(x, z, K) (:50-111, 154-236), with the derivatives of get_coefs'
+coefficients kept, or dropped for ``BPnP_fast`` (:280-341).  The forward's rotation is the exact Rodrigues formula (cv2's); the
+backward differentiates the rotation the reference's backward uses (kornia's: axis = w / (theta + 1e-6), first-order below
+theta^2 = 1e-6), whose ~1e-6 / theta relative difference the 6 x 6 inverse amplifies to ~2e-4 of the gradients at theta ~ 0.14.
+A singular J_fy gives NaN gradients for that sample (the reference raises in torch.inverse)."""
+import torch
+
+from hrpe_amd import _native as nv
+from hrpe_amd.lib.utils.geometries import angle_axis_to_rotation_matrix
+from hrpe_amd.lib.utils.transforms import point_projection_from_3d_tensor
+
+
+def _check(pts2d, pts3d, K, ini_pose, shared):
+    for name, t in (("pts2d", pts2d), ("pts3d", pts3d), ("K", K)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise ValueError(f"BPnP: {name} must be a CUDA tensor (there is no CPU path)")
+    if pts2d.dim() != 3 or pts2d.shape[2] != 2:
+        raise ValueError(f"BPnP: pts2d must be [B, n, 2], got {tuple(pts2d.shape)}")
+    B, n = pts2d.shape[0], pts2d.shape[1]
+    if n < 4 or n > 64:
+        raise ValueError(f"BPnP: {n} points; the solver needs 4 <= n <= 64")
+    want = (n, 3) if shared else (B, n, 3)
+    if tuple(pts3d.shape) != want:
+        raise ValueError(f"BPnP: pts3d must be {list(want)}, got {list(pts3d.shape)}")
+    if tuple(K.shape) not in ((3, 3), (B, 3, 3)):
+        raise ValueError(f"BPnP: K must be [3, 3] or [B, 3, 3], got {list(K.shape)}")
+    if ini_pose is not None and tuple(ini_pose.shape) != (B, 6):
+        raise ValueError(f"BPnP: ini_pose must be [B, 6], got {list(ini_pose.shape)}")
+
+
+def _f32(t):
+    return t.detach().contiguous().float()
+
+
+def pnp_solve(pts2d, pts3d, K, ini_pose=None, shared=None):
+    """P_6d [B,6], status [B,2] int32 (converged, iterations), rms [B] (reprojection error, px).  No autograd."""
+    if shared is None:
+        shared = pts3d.dim() == 2
+    _check(pts2d, pts3d, K, ini_pose, shared)
+    B, n = pts2d.shape[0], pts2d.shape[1]
+    dev = pts2d.device
+    x, z, k = _f32(pts2d), _f32(pts3d), _f32(K)
+    ini = _f32(ini_pose.to(dev)) if ini_pose is not None else None
+    P = torch.empty(B, 6, device=dev)
+    status = torch.empty(B, 2, dtype=torch.int32, device=dev)
+    rms = torch.empty(B, device=dev)
+    nv.call("hrp_pnp_solve", x.data_ptr(), z.data_ptr(), 0 if shared else 3 * n, k.data_ptr(), 0 if k.dim() == 2 else 9,
+            ini.data_ptr() if ini is not None else None, B, n, P.data_ptr(), status.data_ptr(), rms.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    return P, status, rms
+
+
+def pnp_backward(pts2d, pts3d, K, P_6d, grad_output, fast=False, shared=None):
+    """(grad_x [B,n,2], grad_z [n,3] or [B,n,3], grad_K [3,3] or [B,3,3], status [B] int32: 1 = singular J_fy)."""
+    if shared is None:
+        shared = pts3d.dim() == 2
+    B, n = pts2d.shape[0], pts2d.shape[1]
+    dev = pts2d.device
+    x, z, k, P, g = _f32(pts2d), _f32(pts3d), _f32(K), _f32(P_6d), _f32(grad_output)
+    k_shared = k.dim() == 2
+    gx = torch.empty(B, n, 2, device=dev)
+    gz = torch.empty(B, n, 3, device=dev)
+    gK = torch.empty(B, 3, 3, device=dev)
+    gz_sum = torch.empty(n, 3, device=dev) if shared else None
+    gK_sum = torch.empty(3, 3, device=dev) if k_shared else None
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    nv.call("hrp_pnp_bwd", x.data_ptr(), z.data_ptr(), 0 if shared else 3 * n, k.data_ptr(), 0 if k_shared else 9, P.data_ptr(),
+            g.data_ptr(), B, n, int(fast), gx.data_ptr(), gz.data_ptr(), gK.data_ptr(),
+            gz_sum.data_ptr() if shared else None, gK_sum.data_ptr() if k_shared else None, status.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    return gx, (gz_sum if shared else gz), (gK_sum if k_shared else gK), status
+
+
+def _forward(ctx, shared, pts2d, pts3d, K, ini_pose):
+    _check(pts2d, pts3d, K, ini_pose, shared)
+    P_6d, _, _ = pnp_solve(pts2d, pts3d, K, ini_pose, shared=shared)
+    ctx.save_for_backward(pts2d, P_6d, pts3d, K)
+    return P_6d
+
+
+def _backward(ctx, shared, fast, grad_output):
+    pts2d, P_6d, pts3d, K = ctx.saved_tensors
+    gx, gz, gK, _ = pnp_backward(pts2d, pts3d, K, P_6d, grad_output, fast=fast, shared=shared)
+    return gx.to(pts2d.dtype), gz.to(pts3d.dtype), gK.to(K.dtype), None
+
+
+class BPnP(torch.autograd.Function):
+    """pts3d [n, 3] shared by every sample of the batch (BPnP.py:9-111)."""
+
+    @staticmethod
+    def forward(ctx, pts2d, pts3d, K, ini_pose=None):
+        return _forward(ctx, True, pts2d, pts3d, K, ini_pose)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return _backward(ctx, True, False, grad_output)
+
+
+class BPnP_m3d(torch.autograd.Function):
+    """pts3d [B, n, 3]: sample i's 2-D points correspond to sample i's 3-D points (BPnP.py:114-236)."""
+
+    @staticmethod
+    def forward(ctx, pts2d, pts3d, K, ini_pose=None):
+        return _forward(ctx, False, pts2d, pts3d, K, ini_pose)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return _backward(ctx, False, False, grad_output)
+
+
+class BPnP_fast(torch.autograd.Function):
+    """BPnP with the coefficient derivatives dropped from the backward (BPnP.py:239-341); EPnP start instead of RANSAC."""
+
+    @staticmethod
+    def forward(ctx, pts2d, pts3d, K, ini_pose=None):
+        return _forward(ctx, True, pts2d, pts3d, K, ini_pose)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return _backward(ctx, True, True, grad_output)
+
+
+def batch_project(P, pts3d, K, angle_axis=True):
+    """P [B,6] angle-axis + t (or [B,3,4] with angle_axis=False), pts3d [n,3], K [3,3] -> [B,n,2] (BPnP.py:359-377)."""
+    PM = _pose_matrix(P, angle_axis)
+    bs = PM.shape[0]
+    cam = batch_transform_3d(PM, pts3d, angle_axis=False)
+    return point_projection_from_3d_tensor(K.expand(bs, 3, 3).contiguous(), cam)
+
+
+def batch_transform_3d(P, pts3d, angle_axis=True):
+    """P [B,6] (or [B,3,4]), pts3d [n,3] -> camera-frame points [B,n,3] (BPnP.py:379-392)."""
+    PM = _pose_matrix(P, angle_axis)
+    n = pts3d.shape[0]
+    pts3d_h = torch.cat((pts3d, torch.ones(n, 1, device=pts3d.device, dtype=pts3d.dtype)), dim=-1)
+    return pts3d_h.matmul(PM.transpose(-2, -1))
+
+
+def _pose_matrix(P, angle_axis):
+    if not angle_axis:
+        return P
+    bs = P.shape[0]
+    R = angle_axis_to_rotation_matrix(P[:, 0:3].reshape(bs, 3))
+    return torch.cat((R[:, 0:3, 0:3], P[:, 3:6].reshape(bs, 3, 1)), dim=-1)

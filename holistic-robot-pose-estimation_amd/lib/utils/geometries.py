@@ -41,3 +41,23 @@ def rotmat_to_quat(matrices):
     w4 = 4.0 * w
     q = torch.stack([w, (m[:, 2, 1] - m[:, 1, 2]) / w4, (m[:, 0, 2] - m[:, 2, 0]) / w4, (m[:, 1, 0] - m[:, 0, 1]) / w4], 1)
     return q / torch.clamp(torch.sqrt((q * q).sum(1, keepdim=True)), min=1e-8)
+
+
+def angle_axis_to_rotation_matrix(angle_axis):
+    """Angle-axis [N,3] -> homogeneous rotation [N,4,4] (geometries.py:164-235, the torchgeometry formula): axis = w / (theta + 1e-6),
+    and the first-order form I + [w]x where theta^2 <= 1e-6."""
+    theta2 = (angle_axis * angle_axis).sum(1, keepdim=True)
+    theta = torch.sqrt(theta2)
+    wx, wy, wz = torch.chunk(angle_axis / (theta + 1e-6), 3, dim=1)
+    c, s = torch.cos(theta), torch.sin(theta)
+    k = 1.0 - c
+    normal = torch.cat([c + wx * wx * k, wx * wy * k - wz * s, wy * s + wx * wz * k,
+                        wz * s + wx * wy * k, c + wy * wy * k, -wx * s + wy * wz * k,
+                        -wy * s + wx * wz * k, wx * s + wy * wz * k, c + wz * wz * k], dim=1).view(-1, 3, 3)
+    rx, ry, rz = torch.chunk(angle_axis, 3, dim=1)
+    one = torch.ones_like(rx)
+    taylor = torch.cat([one, -rz, ry, rz, one, -rx, -ry, rx, one], dim=1).view(-1, 3, 3)
+    mask = (theta2 > 1e-6).view(-1, 1, 1).type_as(theta2)
+    out = torch.eye(4, dtype=angle_axis.dtype, device=angle_axis.device).repeat(angle_axis.shape[0], 1, 1)
+    out[:, :3, :3] = mask * normal + (1 - mask) * taylor
+    return out

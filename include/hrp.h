@@ -41,6 +41,10 @@
  *                                                     lib/utils/urdf_robot.py:82-111, 169-199;
  *                                                     lib/utils/urdfpytorch/urdf.py:3115-3140, 2344-2462;
  *                                                     lib/utils/geometries.py:100-115; lib/utils/transforms.py:17-21
+ *   hrp_pnp_solve             BPnP / BPnP_m3d / BPnP_fast forward: cv2.solvePnP EPnP start + iterative LM, one call per sample
+ *                                                     lib/utils/BPnP.py:24-47, 129-151, 255-278
+ *   hrp_pnp_bwd               their backward (implicit-function gradient through get_coefs)
+ *                                                     lib/utils/BPnP.py:50-111, 154-236, 280-341, 344-357
  */
 #ifndef HRP_H
 #define HRP_H
@@ -766,6 +770,25 @@ int hrp_linear_wgrad_batch(const hrp_linear_wgrad_desc* descs, int n, void* stre
 /* point_projection_from_3d_tensor (lib/utils/transforms.py:17-21): K [B,9], pts [B,P,3] -> uv [B,P,2] */
 int hrp_project_fwd(const float* K, const float* pts, int B, int P, float* uv, void* stream);
 int hrp_project_bwd(const float* K, const float* pts, const float* duv, int B, int P, float* dpts, void* stream);
+
+/* Perspective-n-point, one 64-lane workgroup per sample (4 <= n <= 64 points), fp64 inside (csrc/pnp.hip).
+ * hrp_pnp_solve replaces the per-sample host loop of cv2.solvePnP calls in BPnP.forward (lib/utils/BPnP.py:24-47, 129-151):
+ *   EPnP (control points from the PCA of the 3-D points, null space of M^T M by Jacobi, N = 1, 2, 3 beta solutions refined by
+ *   Gauss-Newton, the lowest mean reprojection error kept) unless ini_pose [B,6] is given (:142-145), then Levenberg-Marquardt on
+ *   (angle-axis, t) minimising sum_i |x_i - pi(K, R X_i + t)|^2 with a fixed iteration cap.
+ *   pts2d [B,n,2]; pts3d [B,n,3] (pts3d_stride = 3n) or shared [n,3] (0); K [B,3,3] (K_stride = 9) or shared [3,3] (0).
+ *   P6d [B,6] = angle-axis (|w| <= pi) then translation.  status [B,2] = (converged, iterations) and rms [B] (reprojection error
+ *   in px at the solution) are optional (NULL).
+ * hrp_pnp_bwd replaces BPnP.backward (:50-111), BPnP_m3d.backward (:154-236) and, with fast = 1, BPnP_fast.backward (:280-341): the
+ *   reference's formula grad = -g^T J_fy^-1 J_f(x, z, K) with f_j = sum_i coef_ij . (x_i S_i - (K [R|t] z_i)_{0:2}), coef = -2 dpi/dy
+ *   (get_coefs :344-357, whose create_graph=True derivatives are kept unless fast).  grad_x [B,n,2]; grad_z [B,n,3] and grad_K [B,9]
+ *   per sample; grad_z_sum [n,3] / grad_K_sum [9] (optional) their sums over the batch in sample order (shared pts3d / K).
+ *   A singular J_fy gives NaN gradients for that sample and status[b] = 1 (optional [B]); the reference raises in torch.inverse. */
+int hrp_pnp_solve(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* ini_pose,
+                  int B, int n, float* P6d, int* status, float* rms, void* stream);
+int hrp_pnp_bwd(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
+                const float* grad_out, int B, int n, int fast, float* grad_x, float* grad_z, float* grad_K, float* grad_z_sum,
+                float* grad_K_sum, int* status, void* stream);
 
 #ifdef __cplusplus
 }
