@@ -210,6 +210,19 @@ class FkChain(C.Structure):
                 ("kp_offset", (C.c_float * 3) * FK_MAX_KP), ("dof", C.c_int32)]
 
 
+DREAM_BANDS = 32
+DREAM_JITTER, DREAM_OCCLUSION, DREAM_SHARPNESS, DREAM_CONTRAST, DREAM_BRIGHTNESS, DREAM_COLOR = 1, 2, 4, 8, 16, 32
+
+
+class DreamSample(C.Structure):
+    _fields_ = [("jitter", C.c_double * 3), ("enh", C.c_double * 4), ("flags", C.c_int32),
+                ("occ_x", C.c_int32), ("occ_y", C.c_int32), ("occ_w", C.c_int32), ("occ_h", C.c_int32),
+                ("pad_x", C.c_int32), ("pad_y", C.c_int32), ("work_w", C.c_int32), ("work_h", C.c_int32),
+                ("crop_x0", C.c_int32), ("crop_y0", C.c_int32), ("crop_x1", C.c_int32), ("crop_y1", C.c_int32),
+                ("off_x", C.c_int32), ("off_y", C.c_int32), ("side", C.c_int32), ("reserved", C.c_int32),
+                ("noise_off", C.c_int64), ("scratch_off", C.c_int64)]
+
+
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 # name -> argtypes (every function returns int unless noted); mirrors include/hrp.h one to one
 PROTOTYPES = {
@@ -288,6 +301,8 @@ PROTOTYPES = {
     "hrp_project_bwd": [_P, _P, _P, _I, _I, _P, _P],
     "hrp_pnp_solve": [_P, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P],
     "hrp_pnp_bwd": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "hrp_dream_augment": [_P, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P],
+    "hrp_dream_crop_resize": [_P, _L, _P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
 }
 
 _lib = None

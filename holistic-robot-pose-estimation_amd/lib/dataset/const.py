@@ -53,3 +53,12 @@ JOINT_BOUNDS = {
                [-3.0542, 3.0542], [-3.0542, 3.0542], [-0.0500, 2.6180], [-0.0500, 2.6180], [-3.0590, 3.0590],
                [-3.0590, 3.0590], [-1.5708, 2.0940], [-1.5708, 2.0940], [-3.0590, 3.0590], [-3.0590, 3.0590]],
 }
+
+# DREAM annotation key-point names per robot, in the order of the datasets' keypoints_2d / TCO_keypoints_3d (lib/dataset/const.py:12-33)
+KEYPOINT_NAMES = {
+    "panda": ["panda_link0", "panda_link2", "panda_link3", "panda_link4", "panda_link6", "panda_link7", "panda_hand"],
+    "baxter": ["torso_t0", "right_s0", "left_s0", "right_s1", "left_s1", "right_e0", "left_e0", "right_e1", "left_e1",
+               "right_w0", "left_w0", "right_w1", "left_w1", "right_w2", "left_w2", "right_hand", "left_hand"],
+    "kuka": ["iiwa7_link_%d" % i for i in range(8)],
+    "owi535": ["Rotation", "Base", "Elbow", "Wrist"],
+}

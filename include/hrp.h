@@ -45,6 +45,11 @@
  *                                                     lib/utils/BPnP.py:24-47, 129-151, 255-278
  *   hrp_pnp_bwd               their backward (implicit-function gradient through get_coefs)
  *                                                     lib/utils/BPnP.py:50-111, 154-236, 280-341, 344-357
+ *   hrp_dream_augment         DreamDataset's colour jitter, occlusion fill and ImageEnhance.Sharpness over the working frame,
+ *                             and the convert("L") sums of ImageEnhance.Contrast
+ *                                                     lib/dataset/dream.py:226-255; roboutils.py:163-195; augmentations.py:96-123
+ *   hrp_dream_crop_resize     resize_image + CropResizeToAspectAugmentation with the Contrast / Brightness / Color tail
+ *                                                     lib/dataset/roboutils.py:128-156; augmentations.py:96-123, 170-242
  */
 #ifndef HRP_H
 #define HRP_H
@@ -789,6 +794,47 @@ int hrp_pnp_solve(const float* pts2d, const float* pts3d, int pts3d_stride, cons
 int hrp_pnp_bwd(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
                 const float* grad_out, int B, int n, int fast, float* grad_x, float* grad_z, float* grad_K, float* grad_z_sum,
                 float* grad_K_sum, int* status, void* stream);
+
+/* DREAM dataset pixel work (csrc/dream.hip): the host (lib/dataset/dream.py) draws every random number and computes the geometry
+ * of each sample into one hrp_dream_sample; these two launches do the per-pixel steps of a batch, bit-exact with the reference's
+ * numpy / Pillow / torch CPU arithmetic.  Coordinates are in the sample's WORKING frame: the decoded frame or, under
+ * process_truncation (dream.py:226-227, roboutils.py:163-195), its zero-padded copy of work_h x work_w with the decoded frame at
+ * (pad_y, pad_x).
+ * hrp_dream_augment replaces dream.py:229-255 up to the pointwise enhancements.  Per working-frame pixel, in the reference's
+ *   order: jitter (flags & HRP_DREAM_JITTER; uint8 * fp64 jitter[c], clipped to [0, 255], truncated; :229-237), the occlusion fill
+ *   (HRP_DREAM_OCCLUSION; the rectangle occ_* takes its bytes, HWC, from noise + noise_off; :239-245), ImageEnhance.Sharpness
+ *   (HRP_DREAM_SHARPNESS; Image.blend(SMOOTH(im), im, enh[0]), SMOOTH rounding (8 neighbours + 5 centre + 6) / 13 with the
+ *   border pixels kept).  frames: [B, H, W, 3] uint8; scratch: the working frame of sample b, [work_h, work_w, 3] uint8 at
+ *   scratch + scratch_off; lsum: [B, HRP_DREAM_BANDS] uint64, the exact sums of convert("L") ((19595 r + 38470 g + 7471 b +
+ *   2^15) >> 16) of the written frame over HRP_DREAM_BANDS bands of rows (ImageEnhance.Contrast's mean, reduced in band order by
+ *   the crop launch).  max_h / max_w bound every work_h / work_w (the grid does not depend on the table: graph-capturable).
+ * hrp_dream_crop_resize replaces resize_image (roboutils.py:128-156) + CropResizeToAspectAugmentation (augmentations.py:170-242):
+ *   output pixel -> zero-padded side x side canvas (the crop box crop_* of the working frame at (off_x, off_y)) -> torch's CPU
+ *   bilinear (align_corners=False, scale = (float)side / out) over the 4 canvas pixels, each taken through the pointwise tail
+ *   Contrast (enh[1], mean int(sum / pixels + 0.5)), Brightness (enh[2]), Color (enh[3]) with Pillow's uint8 truncation between
+ *   them; v / 255 interpolated, (x * 255) truncated.  side == out size: the canvas itself (augmentations.py:176-178).
+ *   out0 [B, 3, h0, w0] and optionally out1 [B, 3, h1, w1] uint8 (the rootnet and other views when their sizes differ). */
+#define HRP_DREAM_BANDS 32
+enum {
+  HRP_DREAM_JITTER = 1, HRP_DREAM_OCCLUSION = 2, HRP_DREAM_SHARPNESS = 4, HRP_DREAM_CONTRAST = 8, HRP_DREAM_BRIGHTNESS = 16,
+  HRP_DREAM_COLOR = 32
+};
+typedef struct {
+  double jitter[3];   /* per-channel colour-jitter factors (used when flags & HRP_DREAM_JITTER) */
+  double enh[4];      /* Sharpness, Contrast, Brightness, Color factors as drawn (Image.blend takes them as float) */
+  int32_t flags;      /* HRP_DREAM_* of the stages whose draw fired */
+  int32_t occ_x, occ_y, occ_w, occ_h;                 /* occlusion rectangle in the working frame */
+  int32_t pad_x, pad_y, work_w, work_h;               /* decoded frame's offset in the working frame; working-frame size */
+  int32_t crop_x0, crop_y0, crop_x1, crop_y1;         /* resize_image's bbox (wmin, hmin, wmax, hmax) */
+  int32_t off_x, off_y, side;                         /* its offsets in the square canvas, and the canvas side S */
+  int32_t reserved;
+  int64_t noise_off;                                  /* occ_h * occ_w * 3 noise bytes (HWC) */
+  int64_t scratch_off;                                /* byte offset of the working frame in scratch */
+} hrp_dream_sample;
+int hrp_dream_augment(const uint8_t* frames, int B, int H, int W, const hrp_dream_sample* table_dev, const uint8_t* noise,
+                      int64_t noise_bytes, int max_h, int max_w, uint8_t* scratch, int64_t scratch_bytes, uint64_t* lsum, void* stream);
+int hrp_dream_crop_resize(const uint8_t* scratch, int64_t scratch_bytes, const hrp_dream_sample* table_dev, const uint64_t* lsum, int B,
+                          int max_h, int max_w, uint8_t* out0, int h0, int w0, uint8_t* out1, int h1, int w1, void* stream);
 
 #ifdef __cplusplus
 }
