@@ -150,6 +150,17 @@ class PoseLossDesc(C.Structure):
                 ("image_size", C.c_float), ("rot_dim", C.c_int32)]
 
 
+class EvalDesc(C.Structure):
+    """hrp_eval_desc (include/hrp.h): inputs, per-image accumulators, per-batch rows, sizes."""
+    INPUTS = ("pred_kp3d_fk", "pred_kp3d_int", "gt_kp3d", "gt_kp2d", "K", "pred_joint", "gt_joint", "pred_rot", "gt_rot")
+    PER_IMAGE = ("error3d", "error2d", "mean_jointerror", "error_depth", "batch_error_relative", "error3d_relative",
+                 "error3d_int", "error2d_int", "error_depth_int", "batch_error_relative_int", "error3d_relative_int")
+    PER_BATCH = ("dis3d", "dis2d", "dis3d_int", "dis2d_int", "l1_jointerror", "rotation_diff")
+    _fields_ = [(n, C.c_void_p) for n in INPUTS + PER_IMAGE + PER_BATCH] + \
+               [(n, C.c_int32) for n in ("B", "nkp", "dof", "rot_dim", "root", "drop_last_joint", "offset", "capacity",
+                                         "batch_index", "batch_capacity")]
+
+
 OPT_CHUNK = 4096
 
 
@@ -303,6 +314,7 @@ PROTOTYPES = {
     "hrp_pnp_bwd": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "hrp_dream_augment": [_P, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P],
     "hrp_dream_crop_resize": [_P, _L, _P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
+    "hrp_eval_batch": [C.POINTER(EvalDesc), _P],
 }
 
 _lib = None

@@ -5,10 +5,17 @@ function.py:119-120.  What lives here is the caller contract around it, restated
 ``k_values`` (function.py:88-98) without the per-sample Python loop and the loss assembly of
 function.py:191-322 for the ``configs/panda/full.yaml`` choice of loss functions.  These are O(B*7*3)
 element tensor expressions (torch ops, not part of the accelerated path); the two key-point
-projections go through the projection kernel."""
+projections go through the projection kernel.
+
+``farward_loss`` (the reference's spelling) and ``validate`` are the reference's step and validation functions
+(function.py:19-327, 330-417) on top of those pieces; the metrics of a validation batch are one launch (hrp_eval_batch)
+into the device-side accumulators of an ``Evaluator``, read once per epoch."""
+import math
+
+import numpy as np
 import torch
 
-from hrpe_amd.lib.dataset.const import JOINT_NAMES
+from hrpe_amd.lib.dataset.const import INITIAL_JOINT_ANGLE, JOINT_NAMES, JOINT_TO_KP
 from hrpe_amd.lib.utils.geometries import rotmat_to_quat, rotmat_to_rot6d
 from hrpe_amd.lib.utils.transforms import point_projection_from_3d_tensor
 
@@ -272,3 +279,280 @@ def full_loss_expr(pred, gt, K, root=3, image_size=256.0, weights=FULL_YAML_WEIG
             + w["kp3d"] * t["loss_error3d"] + w["kp2d_int"] * t["loss_error2d_int"]
             + w["kp3d_int"] * t["loss_error3d_int"] + w["align_3d"] * t["loss_error3d_align"])
     return loss, t
+
+
+# the choice of loss functions hrp_pose_loss implements: identical in every configs/*/full.yaml
+SHIPPED_LOSS_FUNCS = dict(pose_loss_func="mse", rot_loss_func="mse", trans_loss_func="l2norm", depth_loss_func="l1",
+                          uv_loss_func="l2norm", kp2d_loss_func="l2norm", kp3d_loss_func="l2norm", kp2d_int_loss_func="l2norm",
+                          kp3d_int_loss_func="l2norm", align_3d_loss_func="l2norm")
+LOSS_SLOTS = TERM_NAMES + ("loss",)       # the eleven values an Evaluator keeps per batch
+METRIC_KEYS = ("image_dis3d_avg", "image_dis2d_avg", "batch_dis3d_avg", "batch_dis2d_avg", "batch_l1jointerror_avg",
+               "image_l1jointerror_avg", "root_depth_error", "image_dis3d_avg_int", "image_dis2d_avg_int", "batch_dis3d_avg_int",
+               "batch_dis2d_avg_int", "root_depth_error_int", "rotation_diff")          # function.py:173-179
+
+
+def _opt(args, name, default=None):
+    try:
+        return getattr(args, name)
+    except (AttributeError, KeyError):
+        return default
+
+
+def check_loss_options(args):
+    """NotImplementedError, naming the option, for what the fused loss does not cover (function.py:195-298)."""
+    for name, shipped in SHIPPED_LOSS_FUNCS.items():
+        got = _opt(args, name, shipped)
+        if got != shipped:
+            raise NotImplementedError(f"{name}={got!r}: the fused loss implements {name}={shipped!r} (every configs/*/full.yaml)")
+    if _opt(args, "fix_mask", False):
+        raise NotImplementedError("fix_mask=True: the fused loss has no masked kp3d_int / align_3d terms (function.py:276-278, 294-296)")
+
+
+class Evaluator:
+    """The accumulators of one validation epoch, on the device (reference function.py:337-376: thirteen AverageValueMeters,
+    five lists and a host copy of everything per batch).
+
+    ``add`` is one hrp_eval_batch launch and one copy of the eleven loss values; nothing synchronises with the host until
+    ``summary``.  Per-image values live in ``per_image`` [11, capacity] (rows: nv.EvalDesc.PER_IMAGE), per-batch values in
+    ``dis`` [4, batch_capacity, nkp] (dis3d, dis2d, dis3d_int, dis2d_int), ``l1_joint`` [batch_capacity, dof], ``rot_diff``
+    [batch_capacity] and ``losses`` [batch_capacity, 11] (LOSS_SLOTS).  ``count`` images and ``batches`` batches are filled;
+    the host knows both, so growing (reallocate + copy) needs no synchronisation either."""
+
+    def __init__(self, robot, capacity, reference_keypoint_id=3, device=None, batch_capacity=64):
+        from hrpe_amd import _native as nv
+        self.robot, self.root = robot, int(reference_keypoint_id)
+        self.device = torch.device(device if device is not None else "cuda")
+        self.nkp, self.dof = len(robot.link_names), robot.dof
+        self.capacity, self.batch_capacity = max(int(capacity), 1), max(int(batch_capacity), 1)
+        self.count = self.batches = 0
+        self.last = None                                    # (offset, B, batch index) of the last add
+        self._names = nv.EvalDesc.PER_IMAGE
+        f = dict(dtype=torch.float32, device=self.device)
+        self.per_image = torch.zeros(len(self._names), self.capacity, **f)
+        self.dis = torch.zeros(4, self.batch_capacity, self.nkp, **f)
+        self.l1_joint = torch.zeros(self.batch_capacity, self.dof, **f)
+        self.rot_diff = torch.zeros(self.batch_capacity, **f)
+        self.losses = torch.zeros(self.batch_capacity, len(LOSS_SLOTS), **f)
+
+    def _grow(self, images, batches):
+        if images > self.capacity:
+            cap = max(images, 2 * self.capacity)
+            new = torch.zeros(self.per_image.shape[0], cap, dtype=torch.float32, device=self.device)
+            new[:, :self.count].copy_(self.per_image[:, :self.count])
+            self.per_image, self.capacity = new, cap
+        if batches > self.batch_capacity:
+            cap, n = max(batches, 2 * self.batch_capacity), self.batches
+            for name, dim in (("dis", 1), ("l1_joint", 0), ("rot_diff", 0), ("losses", 0)):
+                old = getattr(self, name)
+                shape = list(old.shape)
+                shape[dim] = cap
+                new = torch.zeros(shape, dtype=torch.float32, device=self.device)
+                new.narrow(dim, 0, n).copy_(old.narrow(dim, 0, n))
+                setattr(self, name, new)
+            self.batch_capacity = cap
+
+    def add(self, pred, gt, loss=None, loss_dict=None):
+        """pred: dict(kp3d_fk [B,nkp,3], kp3d_int [B,nkp,3], joint [B,dof] or None, rot [B,rot_dim]);
+        gt: dict(kp3d, kp2d_original [B,nkp,2], K_original [B,3,3], joint [B,dof], rot [B,rot_dim] - the base rotation).
+        loss / loss_dict: what full_loss returned (optional).  Returns ``metric_dict()`` of this batch."""
+        import ctypes as C
+        from hrpe_amd import _native as nv
+        f32 = lambda t: t.detach().to(self.device, torch.float32, non_blocking=True).contiguous()   # noqa: E731
+        ins = dict(pred_kp3d_fk=f32(pred["kp3d_fk"]), pred_kp3d_int=f32(pred["kp3d_int"]), gt_kp3d=f32(gt["kp3d"]),
+                   gt_kp2d=f32(gt["kp2d_original"]), K=f32(gt["K_original"]), gt_joint=f32(gt["joint"]),
+                   pred_rot=f32(pred["rot"]), gt_rot=f32(gt["rot"]))
+        if pred.get("joint") is not None:
+            ins["pred_joint"] = f32(pred["joint"])
+        B = ins["pred_kp3d_fk"].shape[0]
+        shapes = dict(pred_kp3d_fk=(B, self.nkp, 3), pred_kp3d_int=(B, self.nkp, 3), gt_kp3d=(B, self.nkp, 3), gt_kp2d=(B, self.nkp, 2),
+                      K=(B, 3, 3), gt_joint=(B, self.dof), pred_joint=(B, self.dof), pred_rot=(B, ins["pred_rot"].shape[-1]),
+                      gt_rot=tuple(ins["pred_rot"].shape))
+        for k, t in ins.items():
+            if k in shapes and tuple(t.shape) != shapes[k]:
+                raise nv.HrpError(f"Evaluator.add: {k} is {tuple(t.shape)}, expected {shapes[k]}")
+        self._grow(self.count + B, self.batches + 1)
+        d = nv.EvalDesc()
+        for k, t in ins.items():
+            setattr(d, k, t.data_ptr())
+        for i, k in enumerate(self._names):
+            setattr(d, k, self.per_image[i].data_ptr())
+        for i, k in enumerate(("dis3d", "dis2d", "dis3d_int", "dis2d_int")):
+            setattr(d, k, self.dis[i].data_ptr())
+        d.l1_jointerror, d.rotation_diff = self.l1_joint.data_ptr(), self.rot_diff.data_ptr()
+        d.B, d.nkp, d.dof, d.rot_dim, d.root = B, self.nkp, self.dof, ins["pred_rot"].shape[1], self.root
+        d.drop_last_joint = int(self.robot.robot_type == "panda")                 # metrics.py:84-85
+        d.offset, d.capacity, d.batch_index, d.batch_capacity = self.count, self.capacity, self.batches, self.batch_capacity
+        nv.call("hrp_eval_batch", C.byref(d), torch.cuda.current_stream(self.device).cuda_stream)
+        if loss_dict is not None:
+            torch.stack([loss_dict[n].detach().float().reshape(()) for n in TERM_NAMES] + [loss.detach().float().reshape(())],
+                        out=self.losses[self.batches])
+        self.last = (self.count, B, self.batches)
+        self.count, self.batches = self.count + B, self.batches + 1
+        return self.metric_dict()
+
+    def metric_dict(self):
+        """The thirteen entries of function.py:173-179 for the last batch: views of the accumulators (device tensors)."""
+        o, B, i = self.last
+        im = {n: self.per_image[k, o:o + B] for k, n in enumerate(self._names)}
+        return {"image_dis3d_avg": im["error3d"], "image_dis2d_avg": im["error2d"], "batch_dis3d_avg": self.dis[0, i],
+                "batch_dis2d_avg": self.dis[1, i], "batch_l1jointerror_avg": self.l1_joint[i],
+                "image_l1jointerror_avg": im["mean_jointerror"], "root_depth_error": im["error_depth"],
+                "image_dis3d_avg_int": im["error3d_int"], "image_dis2d_avg_int": im["error2d_int"],
+                "batch_dis3d_avg_int": self.dis[2, i], "batch_dis2d_avg_int": self.dis[3, i],
+                "root_depth_error_int": im["error_depth_int"], "rotation_diff": self.rot_diff[i]}
+
+    def summary(self):
+        """The one synchronisation of the epoch: the accumulators come to the host in one piece each.  Returns the reference's
+        ``summary_add_pck`` of the FK branch at the top level (``['ADD/AUC']`` ...), of the integral branch under ``'integral'`` and
+        of the root-relative errors under ``'relative'`` (scripts/test.py:226-235), and
+          'meters'  the AverageValueMeter means of function.py:337-376 - unweighted means over batches, fp64, in batch order - of
+                    the eleven LOSS_SLOTS, 'rotation_diff', and the vectors 'dis3d', 'dis2d', 'dis3d_int', 'dis2d_int', 'l1_joint';
+          'mean_joint_error' in degrees (function.py:380), 'mean_depth_error', 'relative_depth_error' (scripts/test.py:240-242),
+          'Relative_ADD/AUC' (:254)."""
+        from hrpe_amd.lib.utils.metrics import summary_add_pck
+        n, nb = self.count, self.batches
+        assert n > 0 and nb > 0, "Evaluator.summary: nothing was added"
+        im = dict(zip(self._names, self.per_image[:, :n].cpu()))
+        out = summary_add_pck({"dis3d": im["error3d"], "dis2d": im["error2d"]})
+        out["integral"] = summary_add_pck({"dis3d": im["error3d_int"], "dis2d": im["error2d_int"]})
+        out["relative"] = summary_add_pck({"dis3d": im["error3d_relative"], "dis2d": im["error2d"]})
+
+        def meter(rows):                       # AverageValueMeter: sum of the added values / their number
+            acc = np.zeros(rows.shape[1:], np.float64)
+            for r in rows.double().numpy():
+                acc = acc + r
+            return acc / rows.shape[0]
+        losses = meter(self.losses[:nb].cpu())
+        dis = self.dis[:, :nb].cpu()
+        meters = {k: float(losses[i]) for i, k in enumerate(LOSS_SLOTS)}
+        meters["rotation_diff"] = float(meter(self.rot_diff[:nb].cpu().reshape(nb, 1))[0])
+        for i, k in enumerate(("dis3d", "dis2d", "dis3d_int", "dis2d_int")):
+            meters[k] = meter(dis[i])
+        meters["l1_joint"] = meter(self.l1_joint[:nb].cpu())
+        out["meters"] = meters
+        out["mean_joint_error"] = float(im["mean_jointerror"].double().mean()) / math.pi * 180.0
+        out["mean_depth_error"] = float(im["error_depth"].double().mean())
+        out["relative_depth_error"] = float(im["batch_error_relative"].double().mean())
+        out["Relative_ADD/AUC"] = out["relative"]["ADD/AUC"]
+        return out
+
+
+def farward_loss(args, input_batch, model, robot, device, device_id, train=True, evaluator=None):
+    """The reference's step function (function.py:19-327; its spelling): ``(loss, loss_dict)`` when training, plus
+    ``metric_dict`` (device tensors) when not.  Batch unpacking is ``prepare_batch``, the loss ``full_loss`` (one launch), the
+    metrics one hrp_eval_batch launch into ``evaluator`` (validate passes the epoch's; without one the metrics of this batch
+    alone are computed).  ``device_id`` is the reference's DataParallel list: the model is called as it is (bring it to
+    ``device`` and wrap it for several GPUs - hrpe_amd.parallel - before)."""
+    check_loss_options(args)
+    model.train() if train else model.eval()
+    root = int(args.reference_keypoint_id)
+    rotation_dim = int(_opt(args, "rotation_dim", 6))
+    p = prepare_batch(input_batch, robot, device, reference_keypoint_id=root, use_origin_bbox=bool(_opt(args, "use_origin_bbox", False)),
+                      use_extended_bbox=bool(_opt(args, "use_extended_bbox", True)),
+                      synthetic="synth" in args.train_ds_names, rotation_dim=rotation_dim)                # :66
+    gt = dict(p["gt"])
+    gt_pose_before_mask = gt["pose"]                                                                     # :107
+    if _opt(args, "use_joint_valid_mask", False):                                                        # :104-114
+        valid_mask = torch.as_tensor(input_batch["valid_mask"]).to(device=device, dtype=torch.float32)
+        joint_valid_mask = valid_mask[:, JOINT_TO_KP[robot.robot_type]]
+        assert joint_valid_mask.shape == gt["pose"].shape, (joint_valid_mask.shape, gt["pose"].shape)
+        mean_joints = torch.tensor([INITIAL_JOINT_ANGLE["mean"][robot.robot_type][k] for k in JOINT_NAMES[robot.robot_type]],
+                                   dtype=torch.float32, device=device).unsqueeze(0)
+        gt["pose"] = gt["pose"] * joint_valid_mask + mean_joints * (1 - joint_valid_mask)
+    pred = tuple(model(p["reg_images"], p["root_images"], p["k_values"], K=p["other_K"]))                # :115-120
+    multi_kp = bool(_opt(args, "multi_kp", False))
+    assert len(pred) == (9 if multi_kp else 8), len(pred)
+    pred_pose, pred_rot, pred_trans = pred[0], pred[1], pred[2]
+    if _opt(args, "known_joint", False):                                                                 # :124-125
+        pred_pose = gt["pose"].clone()
+    metric_dict = None
+    if not train:                                                                                        # :137-179
+        if evaluator is None:
+            evaluator = Evaluator(robot, pred_pose.shape[0], reference_keypoint_id=root, device=device, batch_capacity=1)
+        with torch.no_grad():
+            kp3d_fk = robot.get_keypoints_root(pred_pose.detach().float(), pred_rot.detach().float(), pred_trans.detach().float(),
+                                               root=root)                                                # metrics.py:27-34
+        ev_pred = dict(kp3d_fk=kp3d_fk, kp3d_int=pred[-2], joint=pred_pose, rot=pred_rot)
+        # the reference's quirk, kept: rotation_diff compares pred_rot - the rotation at the ROOT key-point - with the BASE
+        # rotation gt_rot, not with gt_root_rot (function.py:169-172); the metrics use the unmasked joint angles (:145)
+        ev_gt = dict(kp3d=gt["kp3d"], kp2d_original=torch.as_tensor(input_batch["keypoints_2d_original"]),
+                     K_original=torch.as_tensor(input_batch["K_original"]), joint=gt_pose_before_mask, rot=gt["rot"])
+    jw = _opt(args, "joint_individual_weights")
+    if jw is not None:                                                                                   # :182-186
+        assert len(jw) == robot.dof
+        w = torch.tensor(list(jw), dtype=torch.float32, device=device).reshape(1, -1)
+        pred_pose, gt["pose"] = pred_pose * w, gt["pose"] * w
+    if _opt(args, "known_joint", False):                                                                 # :188-189
+        pred_pose = gt["pose"].clone()
+    weights = {k: float(_opt(args, k + "_loss_weight", FULL_YAML_WEIGHTS[k])) for k in _WEIGHT_KEYS}
+    loss, loss_dict = full_loss((pred_pose,) + pred[1:], gt, p["other_K"], root=root, image_size=float(_opt(args, "image_size", 256.0)),
+                                weights=weights, kps_need_depth=_opt(args, "kps_need_depth") if multi_kp else None)
+    if train:
+        return loss, loss_dict
+    metric_dict = evaluator.add(ev_pred, ev_gt, loss, loss_dict)
+    return loss, loss_dict, metric_dict
+
+
+ADD_THRESHOLDS = [1, 5, 10, 20, 40, 60, 80, 100]                      # function.py:342-343
+PCK_THRESHOLDS = [2.5, 5.0, 7.5, 10.0, 12.5, 15.0, 17.5, 20.0]
+
+
+def validate(args, epoch, dsname, loader, model, robot, writer, device, device_id):
+    """The reference's validation loop (function.py:330-417): one farward_loss(train=False) per batch into one Evaluator, one
+    summary - the only host synchronisation - at the end, every scalar the reference logs under its tag.  Returns ADD-AUC.
+    ``writer`` may be None.  A loader over this project's DreamDataset (host items with ``frame`` / ``aug``) goes through
+    ``DreamDataset.to_device`` first; a batch already in the reference schema goes straight to ``prepare_batch``."""
+    assert (dsname != "photo" or args.urdf_robot_name != "baxter")          # ds == photo -> not baxter
+    assert (dsname in ["dr", "photo"] or args.urdf_robot_name == "panda")   # ds != dr/photo -> panda
+    ds = "_" + dsname
+    model.eval()
+    dataset = getattr(loader, "dataset", None)
+    try:
+        capacity = len(dataset) if dataset is not None else 0
+    except TypeError:
+        capacity = 0
+    ev = Evaluator(robot, capacity or 1024, reference_keypoint_id=args.reference_keypoint_id, device=device)
+    with torch.no_grad():
+        for sample in loader:
+            if "frame" in sample and "aug" in sample:
+                sample = dataset.to_device(sample, device=device)
+            farward_loss(args=args, input_batch=sample, model=model, robot=robot, device=device, device_id=device_id, train=False,
+                         evaluator=ev)
+    s = ev.summary()
+    if writer is not None:
+        m, s_int = s["meters"], s["integral"]
+        add = lambda tag, v: writer.add_scalar(tag + ds, float(v), epoch)   # noqa: E731
+        add("Val/loss", m["loss"])
+        add("Val/pose_loss", m["loss_joint"])
+        add("Val/rot_loss", m["loss_rot"])
+        add("Val/rot_diff", m["rotation_diff"])
+        add("Val/trans_loss", m["loss_trans"])
+        add("Val/uv_loss", m["loss_uv"])
+        add("Val/depth_loss", m["loss_depth"])
+        add("Val/error2d_loss", m["loss_error2d"])
+        add("Val/error3d_loss", m["loss_error3d"])
+        # as the reference: the two *_int_loss tags log the NON-integral meters (function.py:390-391)
+        add("Val/error2d_int_loss", m["loss_error2d"])
+        add("Val/error3d_int_loss", m["loss_error3d"])
+        add("Val/error3d_align_loss", m["loss_error3d_align"])
+        add("Val/mean_joint_error", s["mean_joint_error"])
+        add("Val/AUC_ADD", s["ADD/AUC"])
+        add("Val/AUC_PCK", s["PCK/AUC"])
+        add("Val/AUC_ADD_integral_xyz_metrics", s_int["ADD/AUC"])
+        add("Val/AUC_PCK_integral_xyz_metrics", s_int["PCK/AUC"])
+        for th in ADD_THRESHOLDS:
+            add(f"Val/ADD_{th}_mm", s[f"ADD_{th}_mm"])
+        for th in PCK_THRESHOLDS:
+            add(f"Val/PCK_{th}_pixel", s[f"PCK_{th}_pixel"])
+        for th in ADD_THRESHOLDS:
+            add(f"Val/ADD_{th}_mm_integral_xyz_metrics", s_int[f"ADD_{th}_mm"])
+        for th in PCK_THRESHOLDS:
+            add(f"Val/PCK_{th}_pixel_integral_xyz_metrics", s_int[f"PCK_{th}_pixel"])
+        for name, suffix in (("dis3d", ""), ("dis2d", ""), ("dis3d_int", "_integral_xyz_metrics"), ("dis2d_int", "_integral_xyz_metrics")):
+            kind = "3D" if name.startswith("dis3d") else "2D"
+            for k in range(ev.nkp):
+                add(f"Val/distance{kind}_keypoint_{k + 1}{suffix}", m[name][k])
+        for k in range(ev.dof):
+            add(f"Val/l1error_joint_{k + 1}", m["l1_joint"][k])
+    model.train()
+    return s["ADD/AUC"]

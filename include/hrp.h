@@ -50,6 +50,10 @@
  *                                                     lib/dataset/dream.py:226-255; roboutils.py:163-195; augmentations.py:96-123
  *   hrp_dream_crop_resize     resize_image + CropResizeToAspectAugmentation with the Contrast / Brightness / Color tail
  *                                                     lib/dataset/roboutils.py:128-156; augmentations.py:96-123, 170-242
+ *   hrp_eval_batch            the validation metrics of one batch (both compute_metrics_batch calls + the geodesic rotation
+ *                             distance) into epoch-length device accumulators
+ *                                                     lib/core/function.py:137-179; lib/utils/metrics.py:36-113;
+ *                                                     lib/utils/geometries.py:21-41, 100-115, 154-162
  */
 #ifndef HRP_H
 #define HRP_H
@@ -835,6 +839,42 @@ int hrp_dream_augment(const uint8_t* frames, int B, int H, int W, const hrp_drea
                       int64_t noise_bytes, int max_h, int max_w, uint8_t* scratch, int64_t scratch_bytes, uint64_t* lsum, void* stream);
 int hrp_dream_crop_resize(const uint8_t* scratch, int64_t scratch_bytes, const hrp_dream_sample* table_dev, const uint64_t* lsum, int B,
                           int max_h, int max_w, uint8_t* out0, int h0, int w0, uint8_t* out1, int h1, int w1, void* stream);
+
+/* Validation metrics of one batch in ONE launch (csrc/eval.hip): what farward_loss(train=False) derives from the predictions
+ * (lib/core/function.py:137-179) - compute_metrics_batch in both call forms (lib/utils/metrics.py:36-113) and the mean geodesic
+ * rotation distance - written straight into accumulators that live on the device for the whole epoch, so that nothing has to
+ * reach the host before the summary.  All tensors dense fp32.  One workgroup; every sum over key-points and over samples runs in
+ * index order (no atomics): bit-reproducible.  NaN where the reference's 0 / 0 gives NaN (an image, or a key-point over the
+ * batch, with nothing in frame).
+ * Per-image outputs are arrays of `capacity` floats, written at [offset, offset + B); per-batch outputs are row-major arrays of
+ * `batch_capacity` rows, written at row batch_index.  offset + B > capacity, batch_index >= batch_capacity, B <= 0, a null
+ * required pointer or rot_dim outside {4, 6}: HRP_ERR_ARG, nothing launches. */
+typedef struct hrp_eval_desc {
+  const float* pred_kp3d_fk;    /* [B,nkp,3] robot.get_keypoints / get_keypoints_root of the predictions   (metrics.py:27-34) */
+  const float* pred_kp3d_int;   /* [B,nkp,3] pred_xyz_integral of the second call          (function.py:166; metrics.py:22-25) */
+  const float* gt_kp3d;         /* [B,nkp,3] gt_keypoints3d                                    (function.py:142; metrics.py:39) */
+  const float* gt_kp2d;         /* [B,nkp,2] gt_keypoints2d_original                           (function.py:143; metrics.py:40) */
+  const float* K;               /* [B,9]     K_original                                    (function.py:144; metrics.py:41-43) */
+  const float* pred_joint;      /* [B,dof]   pred_pose; NULL: zero joint errors            (function.py:146; metrics.py:89-91) */
+  const float* gt_joint;        /* [B,dof]   gt_pose_before_mask (required with pred_joint)    (function.py:145; metrics.py:42) */
+  const float* pred_rot;        /* [B,rot_dim] pred_rot                                                  (function.py:169-172) */
+  const float* gt_rot;          /* [B,rot_dim] gt_rot - the BASE rotation, not the root-relative one     (function.py:169-172) */
+  /* per image, FK branch (metrics.py:57, 67, 85-87, 95, 101, 110) */
+  float *error3d, *error2d, *mean_jointerror, *error_depth, *batch_error_relative, *error3d_relative;
+  /* per image, integral branch (metrics.py:57, 67, 95, 101, 110; its joint errors are zero by definition, :89-91) */
+  float *error3d_int, *error2d_int, *error_depth_int, *batch_error_relative_int, *error3d_relative_int;
+  float *dis3d, *dis2d, *dis3d_int, *dis2d_int;      /* per batch [batch_capacity, nkp] (metrics.py:71-74) */
+  float* l1_jointerror;                              /* per batch [batch_capacity, dof] (metrics.py:83) */
+  float* rotation_diff;                              /* per batch [batch_capacity]: mean_b acos(clamp((tr(Rp Rg^T) - 1) / 2, -1, 1))
+                                                        (geometries.py:154-162; function.py:169-172) */
+  int32_t B, nkp, dof;          /* nkp <= HRP_FK_MAX_KP, dof <= HRP_FK_MAX_JOINTS */
+  int32_t rot_dim;              /* 6: two rows of the matrix (geometries.py:100-115); 4: quaternion w x y z (geometries.py:21-41) */
+  int32_t root;                 /* reference_keypoint_id (metrics.py:94-99) */
+  int32_t drop_last_joint;      /* panda: mean_jointerror leaves the last joint (the finger) out (metrics.py:84-85) */
+  int32_t offset, capacity;     /* first per-image slot of this batch; length of the per-image arrays */
+  int32_t batch_index, batch_capacity;
+} hrp_eval_desc;
+int hrp_eval_batch(const hrp_eval_desc* d, void* stream);
 
 #ifdef __cplusplus
 }
