@@ -5,12 +5,22 @@
 // covers BatchNorm (+ReLU) after a conv, the residual add of BasicBlock / Bottleneck, the whole
 // cross-resolution fuse of HighResolutionModule (BN of each incoming path + nearest upsample + sum +
 // ReLU in ONE pass; reference HRnet.py:256-263 materialises every term), and the cls-head adds.
-// Train-mode BN needs no separate finalize kernel: each workgroup derives scale/shift of its channel slab
+// Train-mode BatchNorm needs no separate finalize kernel: each workgroup derives scale/shift of its channel slab
 // once (into LDS) from the (sum, sumsq) statistic slots the producing conv accumulated in its epilogue.
+//
+// Map of this file.  Three families (EwKind: forward, backward reduce, backward apply), each launched alone
+// (hrp_ew_*) or as one of n problems of a batched launch (HRP_BATCH_EW_*).  Both ways take the same four steps:
+//   predicate  ew_vec_ok      is the descriptor on the 16-byte vector path?  (ew_mask_check: what the bit mask needs)
+//   geometry   ew_geom        (descriptor, n, bytes of the launch) -> block budget -> geom(): V, tpr, slabs, blocks
+//   LDS        ew_lds_bytes   on ew_tabn / ew_nred, the same two helpers that lay out the bodies' dynamic LDS
+//   dispatch   ew_by_dtype, ew_by_vec   element type and instance
+// Bodies: ew_fwd_body, ew_bwd_reduce_body, ew_bwd_apply_body, each a four-pixel trip and a one-pixel tail; shared
+// steps: load_consts (channel constants), pooled_grad (upsampled inputs), reduce_pixels.
 #include "hrp_common.h"
 #include "batch.h"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 namespace hrp {
 
@@ -47,6 +57,14 @@ __device__ __forceinline__ float ew_row_ror(float x) {
 
 constexpr int TAB_CH = 512;  // channels per block whose constants are shared through LDS
 
+// Dynamic LDS of a block of tpr vector columns of V channels (floats): rows of ew_tabn channel constants - 4 (forward,
+// reduce) or 6 (apply: + the two rows of batch sums) - and, in the reduce pass, two arrays of ew_nred partial sums:
+// one partial per wave (tpr < 64) or per thread (tpr >= 64, then 256 / tpr threads share a channel).
+// (sized by the launcher: a static worst-case table kept 12-28 KiB of LDS per block away from the conv / wgrad
+// workgroups of other lanes sharing the CU)
+__host__ __device__ constexpr int ew_tabn(int tpr, int V) { return tpr * V < TAB_CH ? tpr * V : TAB_CH; }
+__host__ __device__ constexpr int ew_nred(int tpr, int V) { return (tpr < 64 ? 4 : 256 / tpr) * tpr * V; }
+
 // scale / shift / mean / invstd of ONE channel of an input
 __device__ __forceinline__ void channel_consts(const hrp_ew_input& in, int c, int C, float& sc, float& sh, float& mean, float& inv) {
   sc = 1.f; sh = 0.f; mean = 0.f; inv = 1.f;
@@ -71,8 +89,7 @@ __device__ __forceinline__ void channel_consts(const hrp_ew_input& in, int c, in
 template <int V>
 __device__ __forceinline__ void load_consts(const hrp_ew_input& in, int C, int cbase, int nch, int c, float* tab,
                                             float* sc, float* sh, float* mean, float* inv) {
-  // tab = 4 rows of nch floats in dynamic LDS (sized by the launcher: a static worst-case table kept 12-28 KiB
-  // of LDS per block away from the conv / wgrad workgroups of other lanes sharing the CU)
+  // tab = 4 rows of nch floats at the start of the dynamic LDS
   if (nch <= TAB_CH) {
     for (int e = threadIdx.x; e < nch; e += 256)
       channel_consts(in, cbase + e, C, tab[e], tab[nch + e], tab[2 * nch + e], tab[3 * nch + e]);
@@ -393,9 +410,9 @@ template <typename T, int V>
 __device__ __forceinline__ void ew_bwd_reduce_body(const hrp_ew_bwd_desc& d, const int tpr, const int bx, const int by, const int gx,
                                                    const int stat_slot) {
   extern __shared__ float ew_lds[];
-  const int tabn = min(tpr * V, TAB_CH);
+  const int tabn = ew_tabn(tpr, V);
   float* tab = ew_lds;
-  const int nred = (tpr < 64 ? 4 : 256 / tpr) * tpr * V;
+  const int nred = ew_nred(tpr, V);
   float* red0 = ew_lds + 4 * tabn;
   float* red1 = red0 + nred;
   const int lane_c = threadIdx.x % tpr;
@@ -489,7 +506,7 @@ __global__ __launch_bounds__(256) void ew_bwd_reduce_kernel(const hrp_ew_bwd_des
 template <typename T, int V, bool LEAKY = false>
 __device__ __forceinline__ void ew_bwd_apply_body(const hrp_ew_bwd_desc& d, const int tpr, const int bx, const int by, const int gx) {
   extern __shared__ float ew_lds[];
-  const int tabn = min(tpr * V, TAB_CH);
+  const int tabn = ew_tabn(tpr, V);
   float* tab = ew_lds;
   float* ktab0 = ew_lds + 4 * tabn;
   float* ktab1 = ktab0 + tabn;
@@ -629,274 +646,39 @@ __global__ __launch_bounds__(256) void ew_bwd_apply_kernel(const hrp_ew_bwd_desc
   ew_bwd_apply_body<T, V, LEAKY>(d, tpr, blockIdx.x, blockIdx.y, gridDim.x);
 }
 
-static inline bool aligned16(const void* p, int pitch, int sz) {
-  return ((uintptr_t)p % 16 == 0) && (((size_t)pitch * sz) % 16 == 0);
-}
-
-struct EwGeom { int V, tpr, nslab, gx; };
-
-// maxblocks: 4 workgroups per CU for the streaming kernels; the reduce kernel uses fewer, each block ends
-// with 2 * channels atomics
-static EwGeom geom(int C, int vec, bool vec_ok, long npix, int maxblocks) {
-  EwGeom g;
-  g.V = (vec_ok && C % vec == 0) ? vec : 1;
-  int nv = C / g.V;
-  int tpr = 1;
-  // at most 64 vector columns (512 channels) per block: the block's channel constants then always go through the
-  // LDS table (per-thread derivation = 16 dependent-latency loads per channel, 10x slower on the 1024 / 2048-channel
-  // ResNet layers); wider tensors are split into channel slabs (grid.y)
-  const int tpr_max = vec_ok && C % vec == 0 ? TAB_CH / vec : 256;
-  while (tpr < nv && tpr < tpr_max && tpr < 256) tpr <<= 1;
-  g.tpr = tpr;
-  g.nslab = cdiv(nv, tpr);
-  int ppb = 256 / tpr;
-  long blocks = (npix + ppb - 1) / ppb;
-  static const int mult = 1;   // (swept: DESIGN 5)
-  long cap = (long)maxblocks * mult / g.nslab;
-  if (cap < 1) cap = 1;
-  g.gx = (int)(blocks < cap ? blocks : cap);
-  if (g.gx < 1) g.gx = 1;
-  return g;
-}
-
-template <typename T>
-static int ew_fwd_t(const hrp_ew_desc& d, hipStream_t s) {
-  constexpr int SZ = Elem<T>::SZ, VEC = Elem<T>::VEC;
-  bool ok = aligned16(d.out, d.out_pitch, SZ);
-  for (int j = 0; j < d.nin; ++j) ok = ok && aligned16(d.in[j].ptr, d.in[j].pitch, SZ);
-  // (one block per CU with 4 pixels in flight per thread: 47.1 ms per step at 1 024 blocks, 46.8 at 512, 46.4 at 256)
-  static const int fwd_blocks = 256;   // (swept: DESIGN 5)
-  bool batched = d.nin <= 2;   // the kernel's four-pixel path; fuse sums (3-4 inputs, upsampled ones) keep 4 blocks per CU
-  for (int j = 0; j < d.nin; ++j) batched = batched && d.in[j].up == 1;
-  EwGeom g = geom(d.C, VEC, ok, (long)d.N * d.H * d.W, batched ? fwd_blocks : 1024);
-  HRP_REQUIRE(!d.mask || (d.relu && g.V == VEC && d.mask_pitch >= d.C / VEC), "ew_fwd: the ReLU bit mask needs relu and the 16-byte vector path");
-  dim3 grid(g.gx, g.nslab);
-  const int tabn = g.tpr * g.V < TAB_CH ? g.tpr * g.V : TAB_CH;
-  const int lds = 4 * tabn * 4;
-  if (d.relu == 2) {      // LeakyReLU: its own instances (rare)
-    if (g.V == 1) hipLaunchKernelGGL((ew_fwd_kernel<T, 1, HRP_EW_MAX_IN, true>), grid, dim3(256), lds, s, d, g.tpr, g.nslab);
-    else hipLaunchKernelGGL((ew_fwd_kernel<T, VEC, HRP_EW_MAX_IN, true>), grid, dim3(256), lds, s, d, g.tpr, g.nslab);
-    return check_launch("ew_fwd");
-  }
-  if (g.V == 1) hipLaunchKernelGGL((ew_fwd_kernel<T, 1, HRP_EW_MAX_IN>), grid, dim3(256), lds, s, d, g.tpr, g.nslab);
-  else if (d.nin <= 2) hipLaunchKernelGGL((ew_fwd_kernel<T, VEC, 2>), grid, dim3(256), lds, s, d, g.tpr, g.nslab);
-  else hipLaunchKernelGGL((ew_fwd_kernel<T, VEC, HRP_EW_MAX_IN>), grid, dim3(256), lds, s, d, g.tpr, g.nslab);
-  return check_launch("ew_fwd");
-}
-
-template <typename T, bool APPLY>
-static int ew_bwd_t(const hrp_ew_bwd_desc& d, hipStream_t s) {
-  constexpr int SZ = Elem<T>::SZ, VEC = Elem<T>::VEC;
-  bool ok = aligned16(d.dout, d.dout_pitch, SZ) && aligned16(d.in.ptr ? d.in.ptr : d.dout, d.in.pitch ? d.in.pitch : d.dout_pitch, SZ);
-  if (d.relu) ok = ok && aligned16(d.out, d.out_pitch, SZ);
-  if (APPLY) ok = ok && aligned16(d.din, d.din_pitch, SZ);
-  if (APPLY && d.din2) ok = ok && aligned16(d.din2, d.din2_pitch, SZ);
-  const int up = d.in.up;
-  static const int red_blocks = 256;   // (swept: DESIGN 5)
-  // (the reduce ends with 2 C atomics per block and keeps 4 pixels of loads in flight per thread: one block per CU
-  // streams as fast alone as 512 and leaves the CUs to the kernels of the other lanes - 48.3 -> 47.6 ms per step;
-  // twice as many on the >= 64 MiB tensors, where the streaming part dominates)
-  const bool big = (int64_t)d.N * d.H * d.W * d.C * SZ >= (64ll << 20);
-  // (apply: 4 pixels of loads in flight per thread and ONE block per CU - 1 024 blocks of one-pixel trips took 9.2 ms
-  // of kernel time per step and a 47.6 ms step, this 9.8 ms and 46.8 ms: the CUs stay free for the other lanes;
-  // block counts that are not a multiple of the 256 CUs (192, 320, 384) lose 0.5-1 ms to the uneven tail)
-  static const int apply_blocks = 256;   // (swept: DESIGN 5)
-  // (the upsampled fuse-layer inputs keep the one-pixel loop: they get the block counts that suited it)
-  const int nblk = up != 1 ? (APPLY ? 1024 : 512) : APPLY ? apply_blocks : (big ? 2 * red_blocks : red_blocks);
-  EwGeom g = geom(d.C, VEC, ok, (long)d.N * (d.H / up) * (d.W / up), nblk);
-  HRP_REQUIRE(!d.mask || (d.relu && g.V == VEC && d.mask_pitch >= d.C / VEC), "ew_bwd: the ReLU bit mask needs relu and the 16-byte vector path");
-  dim3 grid(g.gx, g.nslab);
-  const int tabn = g.tpr * g.V < TAB_CH ? g.tpr * g.V : TAB_CH;
-  if (APPLY) {
-    const int lds = 6 * tabn * 4;
-    if (d.relu == 2) {
-      if (g.V == 1) hipLaunchKernelGGL((ew_bwd_apply_kernel<T, 1, true>), grid, dim3(256), lds, s, d, g.tpr);
-      else hipLaunchKernelGGL((ew_bwd_apply_kernel<T, VEC, true>), grid, dim3(256), lds, s, d, g.tpr);
-    } else if (g.V == 1) hipLaunchKernelGGL((ew_bwd_apply_kernel<T, 1>), grid, dim3(256), lds, s, d, g.tpr);
-    else hipLaunchKernelGGL((ew_bwd_apply_kernel<T, VEC>), grid, dim3(256), lds, s, d, g.tpr);
-  } else {
-    const int nred = (g.tpr < 64 ? 4 : 256 / g.tpr) * g.tpr * g.V;
-    const int lds = (4 * tabn + 2 * nred) * 4;
-    if (g.V == 1) hipLaunchKernelGGL((ew_bwd_reduce_kernel<T, 1>), grid, dim3(256), lds, s, d, g.tpr);
-    else hipLaunchKernelGGL((ew_bwd_reduce_kernel<T, VEC>), grid, dim3(256), lds, s, d, g.tpr);
-  }
-  return check_launch(APPLY ? "ew_bwd_apply" : "ew_bwd_reduce");
-}
-
-
 // ---- batched launches (hrp_batch_*, include/hrp.h) --------------------------------------------------------------
 // n element-wise problems in one launch (the activations of every branch of both trunks after the same layer, all
 // BatchNorm backward passes of a lock-step layer ..).  Vector path only.  The launch's workgroups are shared between
 // the problems in proportion to their bytes, so a workgroup of the [64,64,64,32] tensor and one of the [64,8,8,256]
 // tensor stream about the same amount.
-struct EwProblem { hrp_ew_desc d; int tpr, gx, nslab, pad; FastDiv fd_gx; };
-struct EwBwdProblem { hrp_ew_bwd_desc d; int tpr, gx, nslab, pad; FastDiv fd_gx; };
+template <typename D>
+struct EwProblem { D d; int tpr, gx, nslab, pad; FastDiv fd_gx; };
 
 template <typename T, int MAXIN>
-__global__ __launch_bounds__(256) void ew_fwd_batch_kernel(const EwProblem* __restrict__ tab, const BatchHdr h) {
+__global__ __launch_bounds__(256) void ew_fwd_batch_kernel(const EwProblem<hrp_ew_desc>* __restrict__ tab, const BatchHdr h) {
   int base;
   const int g = batch_find(h, blockIdx.x, base);
-  const EwProblem& P = tab[g];
+  const EwProblem<hrp_ew_desc>& P = tab[g];
   const int local = (int)blockIdx.x - base;
   const int by = fdiv(local, P.fd_gx), bx = local - by * P.gx;
   ew_fwd_body<T, Elem<T>::VEC, MAXIN>(P.d, P.tpr, bx, by, P.gx);
 }
 
 template <typename T, bool APPLY>
-__global__ __launch_bounds__(256) void ew_bwd_batch_kernel(const EwBwdProblem* __restrict__ tab, const BatchHdr h) {
+__global__ __launch_bounds__(256) void ew_bwd_batch_kernel(const EwProblem<hrp_ew_bwd_desc>* __restrict__ tab, const BatchHdr h) {
   int base;
   const int g = batch_find(h, blockIdx.x, base);
-  const EwBwdProblem& P = tab[g];
+  const EwProblem<hrp_ew_bwd_desc>& P = tab[g];
   const int local = (int)blockIdx.x - base;
   const int by = fdiv(local, P.fd_gx), bx = local - by * P.gx;
   if constexpr (APPLY) ew_bwd_apply_body<T, Elem<T>::VEC>(P.d, P.tpr, bx, by, P.gx);
   else ew_bwd_reduce_body<T, Elem<T>::VEC>(P.d, P.tpr, bx, by, P.gx, blockIdx.x & (HRP_STAT_SLOTS - 1));
 }
 
-static int ew_fwd_check(const hrp_ew_desc* d);
-static int ew_bwd_check(const hrp_ew_bwd_desc* d, bool apply);
+// ---- host side: checks -> predicate -> geometry -> LDS -> dispatch ------------------------------------------------
+enum EwKind { EW_FWD, EW_REDUCE, EW_APPLY };
 
-// share of `total` workgroups for a problem of `bytes` out of `sum` (at least `lo`)
-static inline int ew_share(int total, double bytes, double sum, int lo) {
-  int b = (int)(total * bytes / sum + 0.5);
-  return b < lo ? lo : b;
-}
-
-template <typename T>
-static int ew_fwd_batch_prepare(const hrp_ew_desc* descs, int n, EwProblem* tab, hrp_batch_info* info) {
-  constexpr int SZ = Elem<T>::SZ, VEC = Elem<T>::VEC;
-  double bytes[HRP_BATCH_MAX], sum = 0.0;
-  int maxin = 2;
-  for (int i = 0; i < n; ++i) {
-    const hrp_ew_desc& d = descs[i];
-    const int rc = ew_fwd_check(&d);
-    if (rc != HRP_OK) return rc;
-    bool ok = aligned16(d.out, d.out_pitch, SZ) && d.C % VEC == 0;
-    for (int j = 0; j < d.nin; ++j) ok = ok && aligned16(d.in[j].ptr, d.in[j].pitch, SZ);
-    HRP_REQUIRE(ok, "ew batch: problem %d is not on the 16-byte vector path", i);
-    HRP_REQUIRE(d.relu != 2, "ew batch: LeakyReLU problems are launched one by one");
-    HRP_REQUIRE(!d.mask || (d.relu && d.mask_pitch >= d.C / VEC), "ew_fwd: the ReLU bit mask needs relu and the 16-byte vector path");
-    if (d.nin > 2) maxin = HRP_EW_MAX_IN;
-    bytes[i] = (double)d.N * d.H * d.W * d.C * SZ;
-    sum += bytes[i];
-  }
-  // (block budgets swept 256 .. 8192 on the B=64 step: 768 / 384 is the minimum - 43.1 ms at 2048 / 1024, 41.0-41.8 here;
-  // issuing the first trip's loads before the channel-constant phase was measured 0.5 ms slower)
-  static const int total = 768;
-  int blk = 0, lds_max = 0;
-  for (int i = 0; i < n; ++i) {
-    const hrp_ew_desc& d = descs[i];
-    const EwGeom g = geom(d.C, VEC, true, (long)d.N * d.H * d.W, ew_share(n == 1 ? 256 : total, bytes[i], sum, 16));
-    const int tabn = g.tpr * g.V < TAB_CH ? g.tpr * g.V : TAB_CH;
-    lds_max = 4 * tabn * 4 > lds_max ? 4 * tabn * 4 : lds_max;
-    info->blk0[i] = blk;
-    blk += g.gx * g.nslab;
-    if (tab) {
-      memset(&tab[i], 0, sizeof(EwProblem));
-      tab[i].d = d; tab[i].tpr = g.tpr; tab[i].gx = g.gx; tab[i].nslab = g.nslab; tab[i].fd_gx = make_fastdiv(g.gx);
-    }
-  }
-  info->blk0[n] = blk;
-  info->grid = blk; info->lds_bytes = lds_max; info->variant = maxin;
-  return HRP_OK;
-}
-
-template <typename T, bool APPLY>
-static int ew_bwd_batch_prepare(const hrp_ew_bwd_desc* descs, int n, EwBwdProblem* tab, hrp_batch_info* info) {
-  constexpr int SZ = Elem<T>::SZ, VEC = Elem<T>::VEC;
-  double bytes[HRP_BATCH_MAX], sum = 0.0;
-  for (int i = 0; i < n; ++i) {
-    const hrp_ew_bwd_desc& d = descs[i];
-    const int rc = ew_bwd_check(&d, APPLY);
-    if (rc != HRP_OK) return rc;
-    bool ok = aligned16(d.dout, d.dout_pitch, SZ) && aligned16(d.in.ptr ? d.in.ptr : d.dout, d.in.pitch ? d.in.pitch : d.dout_pitch, SZ) &&
-              d.C % VEC == 0;
-    if (d.relu) ok = ok && aligned16(d.out, d.out_pitch, SZ);
-    if (APPLY) ok = ok && aligned16(d.din, d.din_pitch, SZ);
-    if (APPLY && d.din2) ok = ok && aligned16(d.din2, d.din2_pitch, SZ);
-    HRP_REQUIRE(ok, "ew batch: problem %d is not on the 16-byte vector path", i);
-    HRP_REQUIRE(d.relu != 2, "ew batch: LeakyReLU problems are launched one by one");
-    HRP_REQUIRE(!d.mask || (d.relu && d.mask_pitch >= d.C / VEC), "ew_bwd: the ReLU bit mask needs relu and the 16-byte vector path");
-    bytes[i] = (double)d.N * d.H * d.W * d.C * SZ;
-    sum += bytes[i];
-  }
-  static const int total_apply = 768;
-  static const int total_red = 384;
-  int blk = 0, lds_max = 0;
-  for (int i = 0; i < n; ++i) {
-    const hrp_ew_bwd_desc& d = descs[i];
-    const int up = d.in.up;
-    const int share = ew_share(n == 1 ? 256 : (APPLY ? total_apply : total_red), bytes[i], sum, 16);
-    const EwGeom g = geom(d.C, VEC, true, (long)d.N * (d.H / up) * (d.W / up), share);
-    const int tabn = g.tpr * g.V < TAB_CH ? g.tpr * g.V : TAB_CH;
-    int lds;
-    if (APPLY) lds = 6 * tabn * 4;
-    else lds = (4 * tabn + 2 * ((g.tpr < 64 ? 4 : 256 / g.tpr) * g.tpr * g.V)) * 4;
-    lds_max = lds > lds_max ? lds : lds_max;
-    info->blk0[i] = blk;
-    blk += g.gx * g.nslab;
-    if (tab) {
-      memset(&tab[i], 0, sizeof(EwBwdProblem));
-      tab[i].d = d; tab[i].tpr = g.tpr; tab[i].gx = g.gx; tab[i].nslab = g.nslab; tab[i].fd_gx = make_fastdiv(g.gx);
-    }
-  }
-  info->blk0[n] = blk;
-  info->grid = blk; info->lds_bytes = lds_max; info->variant = 0;
-  return HRP_OK;
-}
-
-int ew_batch_prepare(int family, const void* descs, int n, void* table, hrp_batch_info* info) {
-  if (family == HRP_BATCH_EW_FWD) {
-    const hrp_ew_desc* d = (const hrp_ew_desc*)descs;
-    for (int i = 0; i < n; ++i) HRP_REQUIRE(d[i].dtype == d[0].dtype, "ew batch: mixed element types");
-    info->dtype = d[0].dtype;
-    return d[0].dtype == HRP_F32 ? ew_fwd_batch_prepare<float>(d, n, (EwProblem*)table, info)
-                                 : ew_fwd_batch_prepare<bf16_t>(d, n, (EwProblem*)table, info);
-  }
-  const hrp_ew_bwd_desc* d = (const hrp_ew_bwd_desc*)descs;
-  for (int i = 0; i < n; ++i) HRP_REQUIRE(d[i].dtype == d[0].dtype, "ew batch: mixed element types");
-  info->dtype = d[0].dtype;
-  const bool f32 = d[0].dtype == HRP_F32;
-  if (family == HRP_BATCH_EW_BWD_APPLY)
-    return f32 ? ew_bwd_batch_prepare<float, true>(d, n, (EwBwdProblem*)table, info) : ew_bwd_batch_prepare<bf16_t, true>(d, n, (EwBwdProblem*)table, info);
-  return f32 ? ew_bwd_batch_prepare<float, false>(d, n, (EwBwdProblem*)table, info) : ew_bwd_batch_prepare<bf16_t, false>(d, n, (EwBwdProblem*)table, info);
-}
-
-int ew_batch_launch(const void* table_dev, const hrp_batch_info* info, hipStream_t s) {
-  const BatchHdr h = make_hdr(info->blk0, info->n);
-  const dim3 grid(info->grid), block(256);
-  const bool f32 = info->dtype == HRP_F32;
-  if (info->family == HRP_BATCH_EW_FWD) {
-    const EwProblem* tab = (const EwProblem*)table_dev;
-    if (info->variant <= 2) {
-      if (f32) hipLaunchKernelGGL((ew_fwd_batch_kernel<float, 2>), grid, block, info->lds_bytes, s, tab, h);
-      else hipLaunchKernelGGL((ew_fwd_batch_kernel<bf16_t, 2>), grid, block, info->lds_bytes, s, tab, h);
-    } else {
-      if (f32) hipLaunchKernelGGL((ew_fwd_batch_kernel<float, HRP_EW_MAX_IN>), grid, block, info->lds_bytes, s, tab, h);
-      else hipLaunchKernelGGL((ew_fwd_batch_kernel<bf16_t, HRP_EW_MAX_IN>), grid, block, info->lds_bytes, s, tab, h);
-    }
-    return check_launch("ew_fwd_batch_kernel");
-  }
-  const EwBwdProblem* tab = (const EwBwdProblem*)table_dev;
-  if (info->family == HRP_BATCH_EW_BWD_APPLY) {
-    if (f32) hipLaunchKernelGGL((ew_bwd_batch_kernel<float, true>), grid, block, info->lds_bytes, s, tab, h);
-    else hipLaunchKernelGGL((ew_bwd_batch_kernel<bf16_t, true>), grid, block, info->lds_bytes, s, tab, h);
-  } else {
-    if (f32) hipLaunchKernelGGL((ew_bwd_batch_kernel<float, false>), grid, block, info->lds_bytes, s, tab, h);
-    else hipLaunchKernelGGL((ew_bwd_batch_kernel<bf16_t, false>), grid, block, info->lds_bytes, s, tab, h);
-  }
-  return check_launch("ew_bwd_batch_kernel");
-}
-
-int64_t ew_batch_table_bytes(int family, int n) {
-  return (int64_t)n * (family == HRP_BATCH_EW_FWD ? sizeof(EwProblem) : sizeof(EwBwdProblem));
-}
-
-}  // namespace hrp
-
-using namespace hrp;
-
-static int hrp::ew_fwd_check(const hrp_ew_desc* d) {
+static int ew_check(const hrp_ew_desc* d, EwKind) {
   HRP_REQUIRE(d && d->out && d->nin >= 1 && d->nin <= HRP_EW_MAX_IN, "ew_fwd: bad descriptor");
   HRP_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->C > 0, "ew_fwd: empty");
   HRP_REQUIRE((int64_t)d->N * d->H * d->W < (1ll << 31), "ew_fwd: more than 2^31 pixels");
@@ -910,14 +692,8 @@ static int hrp::ew_fwd_check(const hrp_ew_desc* d) {
   return HRP_OK;
 }
 
-extern "C" int hrp_ew_fwd(const hrp_ew_desc* d, void* stream) {
-  const int rc = ew_fwd_check(d);
-  if (rc) return rc;
-  if (d->dtype == HRP_F32) return ew_fwd_t<float>(*d, (hipStream_t)stream);
-  return ew_fwd_t<bf16_t>(*d, (hipStream_t)stream);
-}
-
-static int hrp::ew_bwd_check(const hrp_ew_bwd_desc* d, bool apply) {
+static int ew_check(const hrp_ew_bwd_desc* d, EwKind kind) {
+  const bool apply = kind == EW_APPLY;
   HRP_REQUIRE(d && d->dout, "ew_bwd: bad descriptor");
   HRP_REQUIRE(!d->relu || d->out, "ew_bwd: relu needs the forward output");
   HRP_REQUIRE(d->in.up >= 1 && d->H % d->in.up == 0 && d->W % d->in.up == 0, "ew_bwd: geometry");
@@ -931,11 +707,235 @@ static int hrp::ew_bwd_check(const hrp_ew_bwd_desc* d, bool apply) {
   return HRP_OK;
 }
 
+static inline bool aligned16(const void* p, int pitch, int sz) {
+  return ((uintptr_t)p % 16 == 0) && (((size_t)pitch * sz) % 16 == 0);
+}
+
+// the 16-byte vector path: whole vectors of channels, every operand the kernel touches 16-byte aligned
+template <typename T, EwKind K>
+static bool ew_vec_ok(const hrp_ew_desc& d) {
+  constexpr int SZ = Elem<T>::SZ;
+  bool ok = d.C % Elem<T>::VEC == 0 && aligned16(d.out, d.out_pitch, SZ);
+  for (int j = 0; j < d.nin; ++j) ok = ok && aligned16(d.in[j].ptr, d.in[j].pitch, SZ);
+  return ok;
+}
+template <typename T, EwKind K>
+static bool ew_vec_ok(const hrp_ew_bwd_desc& d) {
+  constexpr int SZ = Elem<T>::SZ;
+  bool ok = d.C % Elem<T>::VEC == 0 && aligned16(d.dout, d.dout_pitch, SZ) &&
+            aligned16(d.in.ptr ? d.in.ptr : d.dout, d.in.pitch ? d.in.pitch : d.dout_pitch, SZ);
+  if (d.relu) ok = ok && aligned16(d.out, d.out_pitch, SZ);
+  if (K == EW_APPLY) ok = ok && aligned16(d.din, d.din_pitch, SZ);
+  if (K == EW_APPLY && d.din2) ok = ok && aligned16(d.din2, d.din2_pitch, SZ);
+  return ok;
+}
+
+// V: the vector width the launch runs with (VEC: the element type's 16-byte vector)
+static int ew_mask_check(const hrp_ew_desc& d, int V, int VEC) {
+  HRP_REQUIRE(!d.mask || (d.relu && V == VEC && d.mask_pitch >= d.C / VEC), "ew_fwd: the ReLU bit mask needs relu and the 16-byte vector path");
+  return HRP_OK;
+}
+static int ew_mask_check(const hrp_ew_bwd_desc& d, int V, int VEC) {
+  HRP_REQUIRE(!d.mask || (d.relu && V == VEC && d.mask_pitch >= d.C / VEC), "ew_bwd: the ReLU bit mask needs relu and the 16-byte vector path");
+  return HRP_OK;
+}
+
+struct EwGeom { int V, tpr, nslab, gx; };
+
+// maxblocks: 4 workgroups per CU for the streaming kernels; the reduce kernel uses fewer, each block ends
+// with 2 * channels atomics
+static EwGeom geom(int C, int V, long npix, int maxblocks) {
+  EwGeom g;
+  g.V = V;
+  int nv = C / g.V;
+  int tpr = 1;
+  // at most 64 vector columns (512 channels) per block: the block's channel constants then always go through the
+  // LDS table (per-thread derivation = 16 dependent-latency loads per channel, 10x slower on the 1024 / 2048-channel
+  // ResNet layers); wider tensors are split into channel slabs (grid.y)
+  const int tpr_max = V > 1 ? TAB_CH / V : 256;
+  while (tpr < nv && tpr < tpr_max && tpr < 256) tpr <<= 1;
+  g.tpr = tpr;
+  g.nslab = cdiv(nv, tpr);
+  int ppb = 256 / tpr;
+  long blocks = (npix + ppb - 1) / ppb;
+  long cap = (long)maxblocks / g.nslab;
+  if (cap < 1) cap = 1;
+  g.gx = (int)(blocks < cap ? blocks : cap);
+  if (g.gx < 1) g.gx = 1;
+  return g;
+}
+
+static int ew_lds_bytes(EwKind kind, const EwGeom& g) {
+  const int tabn = ew_tabn(g.tpr, g.V);
+  return (kind == EW_FWD ? 4 * tabn : kind == EW_APPLY ? 6 * tabn : 4 * tabn + 2 * ew_nred(g.tpr, g.V)) * 4;
+}
+
+template <typename T, typename D>
+static double ew_bytes(const D& d) { return (double)d.N * d.H * d.W * d.C * Elem<T>::SZ; }
+
+// share of `total` workgroups for a problem of `bytes` out of `sum` (at least `lo`)
+static inline int ew_share(int total, double bytes, double sum, int lo) {
+  int b = (int)(total * bytes / sum + 0.5);
+  return b < lo ? lo : b;
+}
+
+// Geometry of one problem.  n == 0: a launch of its own; n >= 1: one of the n problems of a batched launch whose
+// problems hold `sum` bytes together (a batch of one gets 256 blocks, one per CU; every problem at least 16).
+// The block budgets (all swept: DESIGN 5):
+template <typename T, EwKind K>
+static EwGeom ew_geom(const hrp_ew_desc& d, int V, int n, double sum) {
+  // single launch (one block per CU with 4 pixels in flight per thread: 47.1 ms per step at 1 024 blocks, 46.8 at 512,
+  // 46.4 at 256)
+  static const int fwd_blocks = 256;
+  // batched launch (block budgets swept 256 .. 8192 on the B=64 step: 768 / 384 (forward and apply / reduce) is the
+  // minimum - 43.1 ms at 2048 / 1024, 41.0-41.8 here; issuing the first trip's loads before the channel-constant phase
+  // was measured 0.5 ms slower)
+  static const int total = 768;
+  bool batched = d.nin <= 2;   // the kernel's four-pixel path; fuse sums (3-4 inputs, upsampled ones) keep 4 blocks per CU
+  for (int j = 0; j < d.nin; ++j) batched = batched && d.in[j].up == 1;
+  const int nblk = n == 0 ? (batched ? fwd_blocks : 1024) : ew_share(n == 1 ? 256 : total, ew_bytes<T>(d), sum, 16);
+  return geom(d.C, V, (long)d.N * d.H * d.W, nblk);
+}
+template <typename T, EwKind K>
+static EwGeom ew_geom(const hrp_ew_bwd_desc& d, int V, int n, double sum) {
+  constexpr bool APPLY = K == EW_APPLY;
+  const int up = d.in.up;
+  // (the reduce ends with 2 C atomics per block and keeps 4 pixels of loads in flight per thread: one block per CU
+  // streams as fast alone as 512 and leaves the CUs to the kernels of the other lanes - 48.3 -> 47.6 ms per step;
+  // twice as many on the >= 64 MiB tensors, where the streaming part dominates)
+  static const int red_blocks = 256;
+  const bool big = (int64_t)d.N * d.H * d.W * d.C * Elem<T>::SZ >= (64ll << 20);
+  // (apply: 4 pixels of loads in flight per thread and ONE block per CU - 1 024 blocks of one-pixel trips took 9.2 ms
+  // of kernel time per step and a 47.6 ms step, this 9.8 ms and 46.8 ms: the CUs stay free for the other lanes;
+  // block counts that are not a multiple of the 256 CUs (192, 320, 384) lose 0.5-1 ms to the uneven tail)
+  static const int apply_blocks = 256;
+  // batched launch: see the forward's note
+  static const int total_apply = 768, total_red = 384;
+  int nblk;
+  // (the upsampled fuse-layer inputs keep the one-pixel loop: they get the block counts that suited it)
+  if (n == 0) nblk = up != 1 ? (APPLY ? 1024 : 512) : APPLY ? apply_blocks : (big ? 2 * red_blocks : red_blocks);
+  else nblk = ew_share(n == 1 ? 256 : (APPLY ? total_apply : total_red), ew_bytes<T>(d), sum, 16);
+  return geom(d.C, V, (long)d.N * (d.H / up) * (d.W / up), nblk);
+}
+
+// f(Tag of the element type) / f(integral constant of the vector width: 1 or the element type's VEC)
+template <typename T> struct EwTag { using type = T; };
+template <typename F>
+static int ew_by_dtype(int dtype, F&& f) { return dtype == HRP_F32 ? f(EwTag<float>{}) : f(EwTag<bf16_t>{}); }
+template <typename T, typename F>
+static void ew_by_vec(int V, F&& f) {
+  if (V == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, Elem<T>::VEC>{});
+}
+
+template <typename T, EwKind K, typename D>
+static int ew_launch(const D& d, hipStream_t s) {
+  constexpr int VEC = Elem<T>::VEC;
+  const EwGeom g = ew_geom<T, K>(d, ew_vec_ok<T, K>(d) ? VEC : 1, 0, 0.0);
+  if (const int rc = ew_mask_check(d, g.V, VEC)) return rc;
+  const dim3 grid(g.gx, g.nslab);
+  const int lds = ew_lds_bytes(K, g);
+  ew_by_vec<T>(g.V, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    if constexpr (K == EW_FWD) {
+      auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, d, g.tpr, g.nslab); };
+      if (d.relu == 2) return go(ew_fwd_kernel<T, V, HRP_EW_MAX_IN, true>);      // LeakyReLU: its own instances (rare)
+      if constexpr (V > 1) if (d.nin <= 2) return go(ew_fwd_kernel<T, V, 2>);
+      go(ew_fwd_kernel<T, V, HRP_EW_MAX_IN>);
+    } else if constexpr (K == EW_APPLY) {
+      if (d.relu == 2) hipLaunchKernelGGL((ew_bwd_apply_kernel<T, V, true>), grid, dim3(256), lds, s, d, g.tpr);
+      else hipLaunchKernelGGL((ew_bwd_apply_kernel<T, V>), grid, dim3(256), lds, s, d, g.tpr);
+    } else {
+      hipLaunchKernelGGL((ew_bwd_reduce_kernel<T, V>), grid, dim3(256), lds, s, d, g.tpr);
+    }
+  });
+  return check_launch(K == EW_FWD ? "ew_fwd" : K == EW_APPLY ? "ew_bwd_apply" : "ew_bwd_reduce");
+}
+
+template <typename T, EwKind K, typename D>
+static int ew_batch_prepare_t(const D* descs, int n, EwProblem<D>* tab, hrp_batch_info* info) {
+  constexpr int VEC = Elem<T>::VEC;
+  double sum = 0.0;
+  int maxin = 2;
+  for (int i = 0; i < n; ++i) {
+    const D& d = descs[i];
+    if (const int rc = ew_check(&d, K)) return rc;
+    HRP_REQUIRE((ew_vec_ok<T, K>(d)), "ew batch: problem %d is not on the 16-byte vector path", i);
+    HRP_REQUIRE(d.relu != 2, "ew batch: LeakyReLU problems are launched one by one");
+    if (const int rc = ew_mask_check(d, VEC, VEC)) return rc;
+    if constexpr (K == EW_FWD) if (d.nin > 2) maxin = HRP_EW_MAX_IN;
+    sum += ew_bytes<T>(d);
+  }
+  int blk = 0, lds_max = 0;
+  for (int i = 0; i < n; ++i) {
+    const EwGeom g = ew_geom<T, K>(descs[i], VEC, n, sum);
+    const int lds = ew_lds_bytes(K, g);
+    lds_max = lds > lds_max ? lds : lds_max;
+    info->blk0[i] = blk;
+    blk += g.gx * g.nslab;
+    if (tab) {
+      memset(&tab[i], 0, sizeof(tab[i]));
+      tab[i].d = descs[i]; tab[i].tpr = g.tpr; tab[i].gx = g.gx; tab[i].nslab = g.nslab; tab[i].fd_gx = make_fastdiv(g.gx);
+    }
+  }
+  info->blk0[n] = blk;
+  info->grid = blk; info->lds_bytes = lds_max; info->variant = K == EW_FWD ? maxin : 0;
+  return HRP_OK;
+}
+
+template <EwKind K, typename D>
+static int ew_batch_prepare_k(const D* d, int n, void* table, hrp_batch_info* info) {
+  for (int i = 0; i < n; ++i) HRP_REQUIRE(d[i].dtype == d[0].dtype, "ew batch: mixed element types");
+  info->dtype = d[0].dtype;
+  return ew_by_dtype(d[0].dtype, [&](auto t) { return ew_batch_prepare_t<typename decltype(t)::type, K>(d, n, (EwProblem<D>*)table, info); });
+}
+
+int ew_batch_prepare(int family, const void* descs, int n, void* table, hrp_batch_info* info) {
+  if (family == HRP_BATCH_EW_FWD) return ew_batch_prepare_k<EW_FWD>((const hrp_ew_desc*)descs, n, table, info);
+  if (family == HRP_BATCH_EW_BWD_APPLY) return ew_batch_prepare_k<EW_APPLY>((const hrp_ew_bwd_desc*)descs, n, table, info);
+  return ew_batch_prepare_k<EW_REDUCE>((const hrp_ew_bwd_desc*)descs, n, table, info);
+}
+
+int ew_batch_launch(const void* table_dev, const hrp_batch_info* info, hipStream_t s) {
+  const BatchHdr h = make_hdr(info->blk0, info->n);
+  const dim3 grid(info->grid), block(256);
+  return ew_by_dtype(info->dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    auto go = [&](auto kernel, auto* tab) { hipLaunchKernelGGL(kernel, grid, block, info->lds_bytes, s, tab, h); };
+    if (info->family == HRP_BATCH_EW_FWD) {
+      const auto* tab = (const EwProblem<hrp_ew_desc>*)table_dev;
+      if (info->variant <= 2) go(ew_fwd_batch_kernel<T, 2>, tab);
+      else go(ew_fwd_batch_kernel<T, HRP_EW_MAX_IN>, tab);
+      return check_launch("ew_fwd_batch_kernel");
+    }
+    const auto* tab = (const EwProblem<hrp_ew_bwd_desc>*)table_dev;
+    if (info->family == HRP_BATCH_EW_BWD_APPLY) go(ew_bwd_batch_kernel<T, true>, tab);
+    else go(ew_bwd_batch_kernel<T, false>, tab);
+    return check_launch("ew_bwd_batch_kernel");
+  });
+}
+
+int64_t ew_batch_table_bytes(int family, int n) {
+  return (int64_t)n * (family == HRP_BATCH_EW_FWD ? sizeof(EwProblem<hrp_ew_desc>) : sizeof(EwProblem<hrp_ew_bwd_desc>));
+}
+
+}  // namespace hrp
+
+using namespace hrp;
+
+extern "C" int hrp_ew_fwd(const hrp_ew_desc* d, void* stream) {
+  if (const int rc = ew_check(d, EW_FWD)) return rc;
+  return ew_by_dtype(d->dtype, [&](auto t) { return ew_launch<typename decltype(t)::type, EW_FWD>(*d, (hipStream_t)stream); });
+}
+
 extern "C" int hrp_ew_bwd_reduce(const hrp_ew_bwd_desc* d, void* stream) {
-  int rc = ew_bwd_check(d, false);
-  if (rc) return rc;
-  if (d->dtype == HRP_F32) return ew_bwd_t<float, false>(*d, (hipStream_t)stream);
-  return ew_bwd_t<bf16_t, false>(*d, (hipStream_t)stream);
+  if (const int rc = ew_check(d, EW_REDUCE)) return rc;
+  return ew_by_dtype(d->dtype, [&](auto t) { return ew_launch<typename decltype(t)::type, EW_REDUCE>(*d, (hipStream_t)stream); });
+}
+
+extern "C" int hrp_ew_bwd_apply(const hrp_ew_bwd_desc* d, void* stream) {
+  if (const int rc = ew_check(d, EW_APPLY)) return rc;
+  return ew_by_dtype(d->dtype, [&](auto t) { return ew_launch<typename decltype(t)::type, EW_APPLY>(*d, (hipStream_t)stream); });
 }
 
 extern "C" int hrp_ew_pool2(const void* src, int src_dtype, int src_pitch, const uint8_t* mask, int mask_pitch, int N, int H, int W, int C,
@@ -951,11 +951,4 @@ extern "C" int hrp_ew_pool2(const void* src, int src_dtype, int src_pitch, const
   if (src_dtype == HRP_BF16) hipLaunchKernelGGL((ew_pool2_kernel<true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, src_pitch, mask, mask_pitch, N, H, W, C, dst);
   else hipLaunchKernelGGL((ew_pool2_kernel<false>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, src_pitch, mask, mask_pitch, N, H, W, C, dst);
   return check_launch("ew_pool2");
-}
-
-extern "C" int hrp_ew_bwd_apply(const hrp_ew_bwd_desc* d, void* stream) {
-  int rc = ew_bwd_check(d, true);
-  if (rc) return rc;
-  if (d->dtype == HRP_F32) return ew_bwd_t<float, true>(*d, (hipStream_t)stream);
-  return ew_bwd_t<bf16_t, true>(*d, (hipStream_t)stream);
 }

@@ -616,6 +616,64 @@ def test_batch_prepare_is_host_only():
     assert 0 < info.grid <= 512 and 0 < info.grid3 <= 256
 
 
+def _fake_ew(i, dt, N, H, W, Cn, nin=2):
+    d = nv.EwDesc()
+    base = 0x1000000 * (i + 1)
+    d.nin, d.out, d.out_pitch, d.dtype = nin, base, Cn, dt
+    d.N, d.H, d.W, d.C, d.relu = N, H, W, Cn, 1
+    d.mask, d.mask_pitch = base + 0x800000, Cn // (8 if dt == nv.HRP_BF16 else 4)
+    for j in range(nin):
+        e = d.inp[j]
+        e.ptr, e.pitch, e.up, e.mode = base + 0x100000 * (j + 1), Cn, 1, nv.EW_IDENTITY if j else nv.EW_BN_TRAIN
+    e = d.inp[0]
+    e.a, e.b, e.stats, e.count, e.eps = base + 0x900000, base + 0x910000, base + 0x920000, float(N * H * W), 1e-5
+    return d
+
+
+def _fake_ew_bwd(i, dt, N, H, W, Cn, up=1):
+    b = nv.EwBwdDesc()
+    base = 0x1000000 * (i + 1)
+    b.dout, b.out, b.dout_pitch, b.out_pitch = base, base + 0x100000, Cn, Cn
+    b.inp.ptr, b.inp.pitch, b.inp.up, b.inp.mode = base + 0x200000, Cn, up, nv.EW_BN_TRAIN
+    b.inp.a, b.inp.b, b.inp.stats, b.inp.count, b.inp.eps = base + 0x900000, base + 0x910000, base + 0x920000, float(N * H * W // up // up), 1e-5
+    b.din, b.din_pitch, b.sums, b.dtype = base + 0x300000, Cn, base + 0x400000, dt
+    b.N, b.H, b.W, b.C, b.relu = N, H, W, Cn, 1
+    b.mask, b.mask_pitch = base + 0x800000, Cn // (8 if dt == nv.HRP_BF16 else 4)
+    return b
+
+
+def test_elementwise_batch_geometry_is_pinned():
+    """hrp_batch_prepare of the three HRP_BATCH_EW_* families (host only): grid, lds_bytes, variant and blk0 of a handful of tables,
+    and hrp_batch_table_bytes per family, as literals recorded from the library before elementwise.hip's launch plan was unified."""
+    lib = nv.lib()
+    BF, F32 = nv.HRP_BF16, nv.HRP_F32
+    two, slabs, floor = [(2, 64, 64, 32), (2, 8, 8, 256)], [(2, 8, 8, 1024), (2, 16, 16, 512)], [(64, 64, 64, 32), (1, 2, 2, 32), (1, 4, 4, 1024)]
+    # (family, dtype, shapes, nin of problem 0 / up of the even problems) -> (grid, lds_bytes, variant, blk0)
+    cases = [((nv.BATCH_EW_FWD, BF, two, 2), (144, 4096, 2, [0, 128, 144])),
+             ((nv.BATCH_EW_FWD, BF, two, 3), (144, 4096, 4, [0, 128, 144])),
+             ((nv.BATCH_EW_FWD, F32, slabs, 2), (384, 8192, 2, [0, 128, 384])),
+             ((nv.BATCH_EW_FWD, BF, floor, 2), (775, 8192, 2, [0, 766, 767, 775])),        # the small problems are offered the floor of 16 blocks
+             ((nv.BATCH_EW_FWD, BF, [(1, 4, 4, 1024)], 2), (8, 8192, 2, [0, 8])),
+             ((nv.BATCH_EW_BWD_REDUCE, BF, floor, 2), (386, 24576, 0, [0, 383, 384, 386])),
+             ((nv.BATCH_EW_BWD_REDUCE, BF, slabs, 1), (192, 24576, 0, [0, 64, 192])),
+             ((nv.BATCH_EW_BWD_REDUCE, F32, two, 2), (96, 12288, 0, [0, 64, 96])),
+             ((nv.BATCH_EW_BWD_APPLY, F32, two, 1), (288, 6144, 0, [0, 256, 288])),
+             ((nv.BATCH_EW_BWD_APPLY, BF, [(1, 4, 4, 1024)], 2), (2, 12288, 0, [0, 2])),
+             ((nv.BATCH_EW_BWD_APPLY, BF, [(64, 64, 64, 256)], 1), (256, 6144, 0, [0, 256]))]
+    for (fam, dt, shapes, var), want in cases:
+        n = len(shapes)
+        if fam == nv.BATCH_EW_FWD:
+            arr = (nv.EwDesc * n)(*[_fake_ew(i, dt, *s, nin=var if i == 0 else 2) for i, s in enumerate(shapes)])
+        else:
+            arr = (nv.EwBwdDesc * n)(*[_fake_ew_bwd(i, dt, *s, up=var if i % 2 == 0 else 1) for i, s in enumerate(shapes)])
+        host = (C.c_char * int(lib.hrp_batch_table_bytes(fam, n)))()
+        info = nv.BatchInfo()
+        assert lib.hrp_batch_prepare(fam, arr, n, host, C.byref(info)) == 0, lib.hrp_last_error()
+        got = (info.grid, info.lds_bytes, info.variant, list(info.blk0[:n + 1]))
+        assert got == want and info.dtype == dt, (fam, dt, shapes, var, got)
+    assert [int(lib.hrp_batch_table_bytes(f, 1)) for f in (nv.BATCH_EW_FWD, nv.BATCH_EW_BWD_REDUCE, nv.BATCH_EW_BWD_APPLY)] == [328, 208, 208]
+
+
 def test_kernel_choice_and_workspace_queries_are_host_only():
     """Which kernel a convolution problem gets, and the workspace sizes of the ordered reductions, are host decisions that a
     caller can query without a GPU: hrp_conv_rowstrip_channels (3x3 C -> C layers with 4 KiB rows and their fused-BatchNorm
