@@ -161,6 +161,20 @@ class EvalDesc(C.Structure):
                                          "batch_index", "batch_capacity")]
 
 
+DEPTH_LOSS_MAX_KP = 16
+DEPTH_LOSS_KINDS = {"l1": 0, "mse": 1}            # HRP_DEPTH_LOSS_*
+XY_LOSS_KINDS = {None: 0, "l1": 1, "mse": 2}      # HRP_XY_LOSS_*
+
+
+class DepthLossDesc(C.Structure):
+    """hrp_depth_loss_desc (include/hrp.h): inputs, outputs, epoch accumulators, mode and sizes."""
+    POINTERS = ("pred", "gt_root_trans", "gt_kp3d", "mask", "loss", "d_pred", "errors", "losses")
+    _fields_ = [(n, C.c_void_p) for n in POINTERS] + \
+               [(n, C.c_int32) for n in ("B", "W", "J", "nk")] + [("kp_index", C.c_int32 * DEPTH_LOSS_MAX_KP)] + \
+               [(n, C.c_int32) for n in ("depth_loss", "xy_loss", "root_col", "want_grad", "offset", "capacity", "batch_index",
+                                         "batch_capacity")]
+
+
 OPT_CHUNK = 4096
 
 
@@ -315,6 +329,7 @@ PROTOTYPES = {
     "hrp_dream_augment": [_P, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P],
     "hrp_dream_crop_resize": [_P, _L, _P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
     "hrp_eval_batch": [C.POINTER(EvalDesc), _P],
+    "hrp_depth_loss": [C.POINTER(DepthLossDesc), _P],
 }
 
 _lib = None

@@ -54,6 +54,10 @@
  *                             distance) into epoch-length device accumulators
  *                                                     lib/core/function.py:137-179; lib/utils/metrics.py:36-113;
  *                                                     lib/utils/geometries.py:21-41, 100-115, 154-162
+ *   hrp_depth_loss            what the DepthNet trainer's step derives from the model output: the depth loss (l1 | mse; plain,
+ *                             xy branch, multi_kp), its gradient, and the per-image errors of the validation pass into
+ *                             epoch-length device accumulators
+ *                                                     scripts/train_depthnet.py:220-268, 276-303
  */
 #ifndef HRP_H
 #define HRP_H
@@ -875,6 +879,47 @@ typedef struct hrp_eval_desc {
   int32_t batch_index, batch_capacity;
 } hrp_eval_desc;
 int hrp_eval_batch(const hrp_eval_desc* d, void* stream);
+
+/* The DepthNet trainer's step after the model call in ONE launch (csrc/depth_loss.hip): scripts/train_depthnet.py:220-268 - the
+ * loss, its gradient with respect to the model output, and the three per-image errors validate collects (:236-241, :289-301)
+ * written straight into accumulators that live on the device for the whole epoch.  All tensors dense fp32.  The depth is divided by
+ * 1000.0f (not multiplied by 1e-3f) as at :223-232, so the per-image errors are the reference's fp32 values bit for bit.
+ *   plain     (xy_loss none, nk 0, W 1)   loss = L(pred / 1000, gt_root_depth), mean over B                              (:249-252)
+ *   xy branch (xy_loss l1 | mse, W 3)     pred = (x, y, depth).  The depth term is L(pred[:, 2] / 1000, gt_root_depth) with the
+ *             reference's shapes: a [B] prediction against a [B, 1] target, which torch broadcasts - the mean over all B * B
+ *             pairs (p_j / 1000, g_i) (:223, :250).  Added to it: L_xy(pred[:, 0:2] * mask, gt_root_trans[:, 0:2] * mask), mean over
+ *             all 2 B elements (masked rows count in the denominator); the xy columns are not divided by 1000        (:255-259)
+ *   multi_kp  (nk > 0, W nk)              loss = L(pred / 1000, gt_kp3d[:, kp_index, 2]), mean over B * nk              (:263-266)
+ * d_pred (with want_grad): gradient of the loss with respect to pred in mm - l1: sign(e) / n / 1000 with sign(0) = 0 as torch, mse:
+ * 2 e / n / 1000, e = p / 1000 - g; for the xy columns the factor is mask in place of 1 / 1000.
+ * errors (optional) [3, capacity]: |pred[:, root_col] / 1000 - gt_root_depth|, |x - gt_x|, |y - gt_y| per image at
+ * [offset, offset + B); the last two rows receive zeros without the xy branch (:236-241).  With errors, losses[batch_index] receives
+ * the loss as well.  One workgroup; every sum runs in sample order (no atomics): bit-reproducible at any B and offset.
+ * B <= 0, W inconsistent with the mode, root_col >= W, nk > HRP_DEPTH_LOSS_MAX_KP, a kp_index entry >= J, offset + B > capacity,
+ * batch_index >= batch_capacity, an unknown loss kind, want_grad without d_pred or a null required pointer: HRP_ERR_ARG, nothing
+ * launches. */
+#define HRP_DEPTH_LOSS_MAX_KP 16
+enum { HRP_DEPTH_LOSS_L1 = 0, HRP_DEPTH_LOSS_MSE = 1 };
+enum { HRP_XY_LOSS_NONE = 0, HRP_XY_LOSS_L1 = 1, HRP_XY_LOSS_MSE = 2 };
+typedef struct hrp_depth_loss_desc {
+  const float* pred;            /* [B,W] model(images, k_values), depth in mm                                        (:222-232) */
+  const float* gt_root_trans;   /* [B,3] gt_keypoints3d[:, reference_keypoint_id] of the root view, or TCO's t       (:188-194) */
+  const float* gt_kp3d;         /* [B,J,3] gt_keypoints3d of the root view; read with nk > 0 only                        (:197) */
+  const float* mask;            /* [B]   valid_mask_crop[:, reference_keypoint_id] of the root view; xy branch only      (:247) */
+  float* loss;                  /* [1] */
+  float* d_pred;                /* [B,W] or NULL */
+  float* errors;                /* [3,capacity] or NULL: error_depth, error_x, error_y                               (:236-241) */
+  float* losses;                /* [batch_capacity]; required with errors                                                (:291) */
+  int32_t B, W, J, nk;          /* nk <= HRP_DEPTH_LOSS_MAX_KP: len(kps_need_depth), 0 without multi_kp */
+  int32_t kp_index[HRP_DEPTH_LOSS_MAX_KP];   /* kps_need_depth                                                            (:197) */
+  int32_t depth_loss, xy_loss;  /* HRP_DEPTH_LOSS_*, HRP_XY_LOSS_*                                             (:249-254, 256-261) */
+  int32_t root_col;             /* column of pred that is the root depth: 0 (W 1), 2 (xy branch),
+                                   kps_need_depth.index(reference_keypoint_id) (multi_kp)                           (:223, 228-229) */
+  int32_t want_grad;            /* nonzero: write d_pred */
+  int32_t offset, capacity;     /* first per-image slot of this batch; row length of errors */
+  int32_t batch_index, batch_capacity;
+} hrp_depth_loss_desc;
+int hrp_depth_loss(const hrp_depth_loss_desc* d, void* stream);
 
 #ifdef __cplusplus
 }
