@@ -825,6 +825,69 @@ extern "C" int hrp_opt_adam_step(const hrp_opt_tensor* tensors_dev, const hrp_op
   return check_launch("opt_adam_step");
 }
 
+// ---- gradient accumulation over micro-batches: acc = (first ? 0 : acc) + scale * src over a whole gradient arena ------
+// One streaming pass, HBM bound: 16-byte loads / stores, a grid of 256 CUs x 8 workgroups that strides over the arena, two
+// vectors per thread in flight.  MODE 0: first micro-batch (acc is NOT read: stale NaNs cannot leak, no memset in front);
+// MODE 1: accumulate.  SCALED = false is scale == 1: the plain fp32 sum acc + src.  With a scale the product and the sum are
+// rounded separately (never one FMA): the bits of two fp32 element-wise passes.
+constexpr int GACC_THREADS = 256, GACC_MAX_BLOCKS = 256 * 8;
+
+typedef float gacc_f4 __attribute__((ext_vector_type(4)));
+
+// (the pragma keeps the product and the sum two roundings: -ffp-contract=fast would fuse them, __fmul_rn / __fadd_rn included)
+template <int MODE, bool SCALED, typename V>
+__device__ __forceinline__ V gacc_sum(V a, V s, float scale) {
+#pragma clang fp contract(off)
+  V v = s;
+  if (SCALED) v = s * scale;
+  if (MODE) v = a + v;
+  return v;
+}
+template <int MODE, typename V>
+__device__ __forceinline__ V gacc_load(const V* p) {
+  if (MODE) return *p;
+  return V(0.f);
+}
+
+template <int MODE, bool SCALED>
+__global__ __launch_bounds__(GACC_THREADS) void grad_accumulate_kernel(const float* __restrict__ src, float* __restrict__ acc,
+                                                                       int64_t n, float scale) {
+  const int64_t nvec = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * GACC_THREADS;
+  const gacc_f4* __restrict__ s4 = (const gacc_f4*)src;
+  gacc_f4* __restrict__ a4 = (gacc_f4*)acc;
+  int64_t i = (int64_t)blockIdx.x * GACC_THREADS + threadIdx.x;
+  for (; i + stride < nvec; i += 2 * stride) {
+    const gacc_f4 s0 = s4[i], s1 = s4[i + stride];
+    const gacc_f4 a0 = gacc_load<MODE>(a4 + i), a1 = gacc_load<MODE>(a4 + i + stride);
+    a4[i] = gacc_sum<MODE, SCALED>(a0, s0, scale);
+    a4[i + stride] = gacc_sum<MODE, SCALED>(a1, s1, scale);
+  }
+  if (i < nvec) a4[i] = gacc_sum<MODE, SCALED>(gacc_load<MODE>(a4 + i), s4[i], scale);
+  // scalar tail (n % 4 elements): the first threads of workgroup 0
+  const int64_t t = (nvec << 2) + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) acc[t] = gacc_sum<MODE, SCALED>(gacc_load<MODE>(acc + t), src[t], scale);
+}
+
+extern "C" int hrp_grad_accumulate(const float* src, float* acc, int64_t n, int first, float scale, void* stream) {
+  HRP_REQUIRE(src && acc && n > 0, "grad_accumulate: bad args");
+  HRP_REQUIRE((uintptr_t)src % 16 == 0 && (uintptr_t)acc % 16 == 0, "grad_accumulate: src and acc must be 16-byte aligned");
+  HRP_REQUIRE(src != acc, "grad_accumulate: src and acc are the same buffer");
+  const int64_t nvec = n >> 2;
+  const int64_t want = (nvec + 2 * GACC_THREADS - 1) / (2 * GACC_THREADS);   // two vectors per thread and trip
+  const dim3 grid((unsigned)(want < 1 ? 1 : (want > GACC_MAX_BLOCKS ? GACC_MAX_BLOCKS : want))), block(GACC_THREADS);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool scaled = scale != 1.f;
+  if (first) {
+    if (scaled) hipLaunchKernelGGL((grad_accumulate_kernel<0, true>), grid, block, 0, st, src, acc, n, scale);
+    else hipLaunchKernelGGL((grad_accumulate_kernel<0, false>), grid, block, 0, st, src, acc, n, scale);
+  } else {
+    if (scaled) hipLaunchKernelGGL((grad_accumulate_kernel<1, true>), grid, block, 0, st, src, acc, n, scale);
+    else hipLaunchKernelGGL((grad_accumulate_kernel<1, false>), grid, block, 0, st, src, acc, n, scale);
+  }
+  return check_launch("grad_accumulate");
+}
+
 extern "C" int hrp_avgpool_fwd(const void* x, int dtype, int N, int HW, int C, int pitch, float* out, int out_pitch, void* stream) {
   HRP_REQUIRE(x && out && N > 0 && HW > 0 && C > 0, "avgpool_fwd: bad args");
   dim3 grid(cdiv(C, 256), N);

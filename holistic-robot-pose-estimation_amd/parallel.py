@@ -103,6 +103,17 @@ class GradAllReducer:
             out.append((pos, total - pos))
         return out
 
+    def reduce_module(self, module):
+        """The non-overlapped all-reduce of a PlannedModule's gradients, aware of gradient accumulation: call it after every
+        loss.backward().  In the default mode it is `self(module.flat_grads())`.  With set_grad_accumulation(steps > 1) the
+        micro-batches before the last one of a cycle return without any collective (-> False); after the last one the accumulation
+        buffer - module.flat_grads() in that mode - is all-reduced in buckets (-> True).  A cycle that ends early (a short tail of
+        the epoch) is reduced by calling `self(module.flat_grads())` directly.  Every rank must run the same number of micro-batches."""
+        if not module.accumulation_complete():
+            return False
+        self(module.flat_grads())
+        return True
+
     def __call__(self, flats):
         if not collectives_active():
             return

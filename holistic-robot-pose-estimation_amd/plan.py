@@ -499,6 +499,51 @@ def lanes_concurrent(a, b):
     return False
 
 
+class GradAccumulation:
+    """Host state of PlannedModule.set_grad_accumulation(steps > 1): ONE fp32 buffer laid out like the gradient arena of the
+    module's training plans, a view of it per parameter (the parameters' .grad in this mode) and the index of the next micro-batch
+    of the cycle.  Every training plan of one module lays its arena out the same way (Plan.preallocate_param_grads orders the same
+    parameter list), so a full-batch plan and the plan of a trailing partial batch add into the same buffer: the views are keyed by
+    parameter, not by plan.  The buffer is allocated by the first backward in this mode."""
+
+    def __init__(self, steps, average):
+        self.steps = steps
+        self.scale = 1.0 / steps if average else 1.0
+        self.index = 0             # micro-batches accumulated since begin(): the next backward is `first` iff 0
+        self.buf, self.views, self._key = None, {}, None
+
+    def begin(self):
+        self.index = 0
+
+    def complete(self):
+        return self.index >= self.steps
+
+    def bind(self, plan):
+        key = (str(plan.device), plan.grad_arena.numel(), tuple((id(p), off) for p, (off, _) in zip(plan._grad_params, plan._grad_layout)))
+        if key == self._key:
+            return
+        if self.index:
+            raise RuntimeError("gradient accumulation: the set of trainable parameters changed in the middle of a cycle "
+                               "(this plan lays its gradient arena out differently); call begin_accumulation() first")
+        self.buf = torch.zeros_like(plan.grad_arena)
+        self.views = {}
+        for p, (off, n) in zip(plan._grad_params, plan._grad_layout):
+            v = self.buf[off:off + n].view(p.shape)
+            v._hrp_plan_grad = True
+            self.views[id(p)] = v
+        self._key = key
+
+    def accumulate(self, plan, stream):
+        """Behind a complete backward of `plan`, on its stream: buf = (first micro-batch ? 0 : buf) + scale * arena."""
+        self.bind(plan)
+        if self.index >= self.steps:
+            raise RuntimeError(f"gradient accumulation: {self.steps} micro-batches are already in the buffer "
+                               f"(set_grad_accumulation(steps={self.steps})); call begin_accumulation() to start the next cycle")
+        nv.call("hrp_grad_accumulate", plan.grad_arena.data_ptr(), self.buf.data_ptr(), plan.grad_arena.numel(),
+                1 if self.index == 0 else 0, self.scale, stream)
+        self.index += 1
+
+
 class Plan:
     def __init__(self, device, dtype, training, need_grad):
         self.device, self.dtype, self.training, self.need_grad = device, dtype, training, need_grad
@@ -528,6 +573,8 @@ class Plan:
         self.grad_arena = None
         self._grad_views = {}
         self._grad_layout = []
+        self._grad_params = []     # the parameters of _grad_layout, in arena order
+        self.accum = None          # GradAccumulation of the owning module (PlannedModule.set_grad_accumulation(steps > 1))
         self.bwd_split, self.split_active = None, False
         self.bwd_cuts = None       # k cut positions of the backward list (PlannedModule.enable_split_backward(fracs=...))
         self.pre_pack = []         # ops run before the weight packing of every step (derived weight layouts)
@@ -570,6 +617,7 @@ class Plan:
         self.grad_arena = torch.zeros(max(total, 4), dtype=torch.float32, device=self.device)
         off = 0
         self._grad_layout = []     # (offset, numel) in arena order
+        self._grad_params = params
         for p in params:
             self._grad_views[id(p)] = self.grad_arena[off:off + p.numel()].view(p.shape)
             self._grad_views[id(p)]._hrp_plan_grad = True
@@ -862,6 +910,16 @@ class Plan:
         return False
 
     def run_prep(self, force=False):
+        """Pack the weights / fold the eval-mode BatchNorms of this step (force: always; otherwise only when a parameter changed).
+
+        Contract for the gradients: a training plan's grad-enabled forward also zeroes the plan's gradient arena
+        here, early, on the pack stream - and in the default mode the arena IS the parameters' .grad.  So .grad is valid from
+        the end of a backward until the NEXT grad-enabled forward through the same plan: read it, all-reduce it and run
+        optimizer.step() before that forward.  forward, backward, forward, optimizer.step() steps with zeros.  This is not
+        asserted (the host cannot tell a forgotten step from a deliberate second forward); a caller that needs gradients to
+        survive further forwards - or to add up over several backwards - switches on PlannedModule.set_grad_accumulation(steps > 1):
+        .grad then lives in an accumulation buffer that only hrp_grad_accumulate writes, behind each complete backward, and
+        nothing in this function touches it."""
         if not (force or self.params_dirty()):
             return
         s = self._stream()
@@ -967,7 +1025,21 @@ class Plan:
 
     def publish_param_grads(self):
         """Hand the plan-owned gradient buffers to the parameters (torch semantics: .grad holds this
-        backward's gradient; an already-present foreign .grad tensor is accumulated into)."""
+        backward's gradient; an already-present foreign .grad tensor is accumulated into).
+        With gradient accumulation on, .grad is the parameter's view of the module's accumulation buffer instead (marked
+        _hrp_plan_grad like the arena views, so a later plain-mode or second-plan publish replaces it rather than adding to it)."""
+        if self.accum is not None:
+            views = self.accum.views
+            for p, g in self.param_grads.values():
+                t = views.get(id(p))
+                if t is None:
+                    raise RuntimeError("gradient accumulation: a parameter of this plan has no slot in the gradient arena")
+                if p.grad is None or p.grad is t or getattr(p.grad, "_hrp_plan_grad", False):
+                    p.grad = t
+                else:
+                    raise RuntimeError("gradient accumulation: a parameter carries a foreign .grad tensor (not a plan's); "
+                                       "set it to None first - adding the running sum onto it would count micro-batches twice")
+            return
         for p, g in self.param_grads.values():
             # (a .grad that is ANOTHER plan's arena view - a trailing partial batch built a second training plan - holds
             # that plan's last gradient, not something to accumulate onto: this backward's gradient replaces it)

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as nv
-from .plan import Plan, PlanBuilder, _dt
+from .plan import GradAccumulation, Plan, PlanBuilder, _dt
 
 
 def require_gpu(device):
@@ -159,6 +159,9 @@ class Runner:
             self.g_bwd.replay()
         else:
             p.run_backward("first" if p.split_active else None)   # (split: the caller runs plan.run_backward("rest"))
+        if p.accum is not None:
+            # behind the complete backward (hrp_bn_param_grad included) and OUTSIDE its captured graph: `first` is host state
+            p.accum.accumulate(p, s)
         p.publish_param_grads()
         gin = []
         for n in self.in_names:
@@ -202,6 +205,7 @@ class PlannedModule(nn.Module):
         object.__setattr__(self, "_bn_sig", (-1, []))
         object.__setattr__(self, "_compute_dtype", torch.float32)
         object.__setattr__(self, "_x3", False)
+        object.__setattr__(self, "_accum", None)
 
     # compute dtype of the convolution trunk (heads stay fp32)
     def set_compute_dtype(self, dtype):
@@ -224,8 +228,54 @@ class PlannedModule(nn.Module):
         return self._compute_dtype
 
     def flat_grads(self):
-        """Flat fp32 gradient arena of the training plan(s) (views of it are the parameters' .grad)."""
+        """Flat fp32 gradient arena of the training plan(s) (views of it are the parameters' .grad).  With gradient accumulation
+        on: the one accumulation buffer instead (empty list before the first backward in that mode)."""
+        if self._accum is not None:
+            return [self._accum.buf] if self._accum.buf is not None else []
         return [r.plan.grad_arena for r in self._plans.values() if r.plan.grad_arena is not None]
+
+    def set_grad_accumulation(self, steps, average=False):
+        """Gradient accumulation over micro-batches: with steps > 1, up to `steps` backward passes through this module add their
+        parameter gradients up before the optimizer steps.  .grad of every parameter then is a view of ONE accumulation buffer
+        (laid out like the plans' gradient arena, allocated by the first backward in this mode); behind each complete backward
+        hrp_grad_accumulate adds the plan's arena into it - the first micro-batch of a cycle overwrites, the others add.  All
+        training plans of the module share the buffer (a full batch and a trailing partial batch add up), and no forward touches
+        it: gradients survive further grad-enabled forwards (compare Plan.run_prep).
+
+        The micro-batch index is host state of the module, reset ONLY by begin_accumulation(): call it where the loop would call
+        optimizer.zero_grad(), once per cycle (setting the mode begins the first cycle).  A cycle may end early (fewer than `steps`
+        backward passes, then optimizer.step()); a backward beyond `steps` without begin_accumulation() raises RuntimeError.
+        Zeroing or dropping .grad is neither needed nor what resets the index.
+
+        average=False (PyTorch's semantics): the plain fp32 sum - the caller divides the loss.  average=True: every micro-batch
+        enters with the weight 1 / steps.  steps == 1 restores the default mode exactly (.grad is the arena view again and the
+        buffer is released).  Not combinable with enable_split_backward().  Applies to this module and the PlannedModules inside it,
+        each of which accumulates the backward passes of its OWN forward calls."""
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"set_grad_accumulation: steps must be an integer >= 1 (got {steps!r})")
+        mods = [m for m in self.modules() if isinstance(m, PlannedModule)]
+        if steps > 1 and any(r.plan.split_active for m in mods for r in m._plans.values()):
+            raise ValueError("set_grad_accumulation(steps > 1) cannot be combined with enable_split_backward(): the overlapped "
+                             "all-reduce hands out arena ranges of a single backward; call disable_split_backward() first")
+        for m in mods:
+            acc = GradAccumulation(steps, bool(average)) if steps > 1 else None
+            object.__setattr__(m, "_accum", acc)
+            for r in m._plans.values():
+                r.plan.accum = acc if r.plan.need_grad else None
+        return self
+
+    def begin_accumulation(self):
+        """Start the next accumulation cycle: the next backward through this module overwrites the accumulation buffer instead of
+        adding to it.  No device work.  A no-op in the default mode."""
+        for m in self.modules():
+            if isinstance(m, PlannedModule) and m._accum is not None:
+                m._accum.begin()
+        return self
+
+    def accumulation_complete(self):
+        """True when the gradients are ready for the all-reduce / optimizer: always in the default mode; with accumulation on,
+        once `steps` micro-batches of the current cycle are in the buffer."""
+        return self._accum is None or self._accum.complete()
 
     def enable_split_backward(self, min_frac=0.55, fracs=None):
         """Data-parallel overlap: from now on a backward through this module runs only the first part of the training
@@ -236,6 +286,9 @@ class PlannedModule(nn.Module):
         ``plan.run_backward(("seg", j))`` for j = 1 .. k - and the return value is (plan, [ranges_0, .., ranges_{k-1}]): ranges_j
         are final once segment j has run, so each can travel while the next segment computes and only the gradients of the
         last segment (the stems and first stages: a few per cent of the bytes) are reduced behind the backward."""
+        if self._accum is not None:
+            raise ValueError("enable_split_backward() cannot be combined with set_grad_accumulation(steps > 1): the ranges it hands "
+                             "out are final for ONE backward, not for the accumulated sum; call set_grad_accumulation(1) first")
         runners = [r for r in self._plans.values() if r.plan.grad_arena is not None]
         if len(runners) != 1:
             return None
@@ -295,6 +348,8 @@ class PlannedModule(nn.Module):
         for m in self.modules():
             if isinstance(m, PlannedModule):
                 m._plans.clear()
+                if m._accum is not None:       # (parameters moved: the accumulation buffer goes with the plans, the mode stays)
+                    object.__setattr__(m, "_accum", GradAccumulation(m._accum.steps, m._accum.scale != 1.0))
 
     def _apply(self, fn, *a, **k):
         # parameters moved / cast: cached plans hold stale pointers
@@ -349,6 +404,7 @@ class PlannedModule(nn.Module):
             plan.x3 = bool(self._x3)
             if need_grad:
                 plan.preallocate_param_grads(list(self.parameters()))
+                plan.accum = self._accum
             pb = PlanBuilder(plan)
             in_names, outs, img_inputs = self._build(pb, *tensors)
             for kind, h, shape in outs:

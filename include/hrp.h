@@ -435,6 +435,12 @@ int hrp_opt_grad_sumsq(const hrp_opt_tensor* tensors_dev, const hrp_opt_chunk* c
 int hrp_opt_adam_step(const hrp_opt_tensor* tensors_dev, const hrp_opt_chunk* chunks_dev, int nchunks,
                       const float* sumsq_slots, float max_norm, const float* step_dev,
                       float lr, float beta1, float beta2, float eps, void* stream);
+/* Gradient accumulation over micro-batches (PlannedModule.set_grad_accumulation): one streaming pass over a plan's flat
+ * gradient arena,   acc[i] = (first ? 0 : acc[i]) + scale * src[i]   fp32, n elements, src and acc 16-byte aligned and
+ * distinct.  first != 0 does not read acc (whatever it held, NaNs included, is overwritten: no memset in front).  scale == 1
+ * gives the exact fp32 sum acc + src; any other scale rounds the product and the sum separately (no FMA): the bits of
+ * acc + (src * scale) formed by two fp32 element-wise passes. */
+int hrp_grad_accumulate(const float* src, float* acc, int64_t n, int first, float scale, void* stream);
 
 int hrp_ew_fwd(const hrp_ew_desc* d, void* stream);
 int hrp_ew_bwd_reduce(const hrp_ew_bwd_desc* d, void* stream);
