@@ -16,7 +16,7 @@ struct ConvProblem {
   hrp_conv_desc d;
   ConvTiling t;
   int cfg;        // 0: 256 px x 32 cout, 1: 128 px x 32, 2: 256 px x 64, 3: 128 px x 64, 4: 0 with persistent workgroups,
-                  // 5 / 6 / 7 / 8: row-strip kernels (conv_row.h) for 32 / 64 / 128 / 256 channels; 9 / 10: whole-image kernels, 128 / 256
+                  // 5 .. 10: the row-strip family (conv_row.h: row_variant)
   int pgrid;      // cfg 4: workgroups of this problem
   int pad[2];
   RowPlan r;      // cfg 5 / 6
@@ -65,10 +65,10 @@ static int conv_batch_plan_one(const hrp_conv_desc& d, ConvProblem& P, int& lds)
     if (rc_) {   // the lean kernel of the high-resolution BasicBlock layers
       row_plan(d, P.r);
       P.t = ConvTiling{};
-      P.t.nblocks = row_grid(P.r, rc_);
-      P.cfg = rc_ == 32 ? 5 : rc_ == 64 ? 6 : rc_ == 128 ? 7 : 8;
-      if (P.r.img) P.cfg += 2;
-      lds = row_lds_bytes(rc_, P.r.img);
+      const RowVariant v = row_variant(rc_, P.r);      // (a batch keeps the whole-image form of a 128-channel problem: launch_conv_row)
+      P.t.nblocks = v.grid;
+      P.cfg = v.cfg;
+      lds = v.lds_bytes;
       return HRP_OK;
     }
   }

@@ -101,7 +101,7 @@ __device__ __forceinline__ void blk_body(const BlkProblem& q, const int wg) {
   // output channel 16 h + 4 q + i, so that a lane's 16 accumulators are 16 consecutive channels of one pixel)
   bf16x8 wf[9][KS];
   {
-    const int co_lane = m * 32 + 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+    const int co_lane = m * 32 + row_wlane(l31);
     const char* wl = (const char*)(role == 0 ? q.w1 : q.w2) + co_lane * ROW + half * 16;
     const int wnt = role == 0 ? q.w1_ntaps : q.w2_ntaps;
 #pragma unroll

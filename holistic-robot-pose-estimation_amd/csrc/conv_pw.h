@@ -112,10 +112,10 @@ __device__ __forceinline__ void conv_pw_body_t(const hrp_conv_desc& d, const PwP
     __syncthreads();
   }
 
-  // ---- weights: MFMA row rho = l31 carries output channel 16 ((rho >> 2) & 1) + 4 (rho >> 3) + (rho & 3) of the block
+  // ---- weights (lane -> weight row: row_wlane, conv_row.h)
   bf16x8 wf[MW][KS];
   {
-    const int co_lane = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+    const int co_lane = row_wlane(l31);
     const char* wl = (const char*)d.w + (size_t)(d.wtap[0] * d.w_cout_pad + cbase + co_lane) * ROW + half * 16;
     const size_t kstride = (size_t)d.w_ntaps * d.w_cout_pad * ROW;
 #pragma unroll
@@ -254,8 +254,7 @@ __device__ __forceinline__ void conv_pw_body_t(const hrp_conv_desc& d, const PwP
         }
       }
       float s1[16], s2[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s1[i] = s2[i] = 0.f;
+      row_zero_sums(s1, s2);
       const int cl = cbase + mi * 32 + 16 * half;
       const unsigned off[1] = {(unsigned)(pix * Cout + cl) * 2u};
       if (tstats) {
@@ -312,7 +311,7 @@ __device__ __forceinline__ void conv_pw_body_t(const hrp_conv_desc& d, const PwP
 #pragma unroll
     for (int mi = 0; mi < MW; ++mi) {
       if (tstats) {
-        const int co_lane = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+        const int co_lane = row_wlane(l31);
         atomicAdd(d.stats + stat_slot * 2 * Cout + half * Cout + cbase + mi * 32 + co_lane, (double)v[mi]);
       } else {
         row_stats_commit(d, v[mi], l31, cbase + mi * 32 + 16 * half, ctab, Cout, bnb, stat_slot);
@@ -351,7 +350,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_tail_kernel(const hrp_conv_des
   const int grp = bid % p.groups, wg = bid / p.groups;
   const int wci = wave % p.wc, wpi = wave / p.wc;
   const int cbase = (grp * p.wc + wci) * (32 * MW);
-  const int co_lane = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+  const int co_lane = row_wlane(l31);
 
   bf16x8 wf[MW][KS];
   {
@@ -653,7 +652,7 @@ __global__ __launch_bounds__(256, 2) void conv_pw_tail2_kernel(const hrp_conv_de
   const int grp = bid % p.groups, wg = bid / p.groups;
   const int wci = wave % p.wc, wpi = wave / p.wc;
   const int cbase = (grp * p.wc + wci) * (32 * MW);
-  const int co_lane = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+  const int co_lane = row_wlane(l31);
   for (int c = tid; c < Cout; c += 256) {
     float mean, inv, sc, sh, sc2, sh2;
     row_bn_consts(d.tail_stats, d.tail_gamma, d.tail_beta, d.tail_count, d.tail_eps, c, Cout, mean, inv, sc, sh);

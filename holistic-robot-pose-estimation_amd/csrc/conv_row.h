@@ -79,6 +79,31 @@ __device__ __forceinline__ void row_bn_consts(const double* stats, const float* 
   sh = beta[c] - m * sc;
 }
 
+// The per-channel constant table of a workgroup (LDS, [10][C] floats), one channel per call; the bodies keep their own
+// thread-to-channel mapping.
+//   0 sc, 1 sh        of pro_stats  (prologue 1 / 2 / 3: act = fma(x, sc, sh))
+//   2 a = invstd, 3 b = -mean * invstd, 4 k0 = sum g / n, 5 k1 = sum g xhat / n     (prologue 2, sums from pro_bsums)
+//   6 a, 7 b, 8 sc, 9 sh   of bnb_stats (epilogue reduce)
+template <int C>
+__device__ __forceinline__ void row_ctab_pro(const hrp_conv_desc& d, float* ctab, const int c) {
+  float mean, inv, sc, sh;
+  row_bn_consts(d.pro_stats, d.pro_gamma, d.pro_beta, d.pro_count, d.pro_eps, c, C, mean, inv, sc, sh);
+  ctab[0 * C + c] = sc; ctab[1 * C + c] = sh;
+  if (d.pro_mode == 2) {
+    ctab[2 * C + c] = inv; ctab[3 * C + c] = -mean * inv;
+    ctab[4 * C + c] = slot_sum(d.pro_bsums, c, 2 * C) / d.pro_count;
+    ctab[5 * C + c] = slot_sum(d.pro_bsums, C + c, 2 * C) / d.pro_count;
+  }
+}
+
+template <int C>
+__device__ __forceinline__ void row_ctab_bnb(const hrp_conv_desc& d, float* ctab, const int c) {
+  float mean, inv, sc, sh;
+  row_bn_consts(d.bnb_stats, d.bnb_gamma, d.bnb_beta, d.bnb_count, d.bnb_eps, c, C, mean, inv, sc, sh);
+  ctab[8 * C + c] = sc; ctab[9 * C + c] = sh;
+  ctab[6 * C + c] = inv; ctab[7 * C + c] = -mean * inv;
+}
+
 // the relu(bn(.)) of the forward prologue and the mask of both backward uses: ONE expression, so that the three agree bit for bit
 __device__ __forceinline__ float row_bn_act(float x, float sc, float sh) { return fmaf(x, sc, sh); }
 
@@ -130,6 +155,11 @@ static inline void row_plan(const hrp_conv_desc& d, RowPlan& rp) {
   }
 }
 
+
+// Weight row of a lane: MFMA row rho = l31 = 8 q + 4 h + i carries output channel 16 h + 4 q + i of the wave's 32-channel block,
+// so that accumulator register 4 q + i of a lane (half h) is channel 16 h + 4 q + i: a lane's 16 accumulators are 16 CONSECUTIVE
+// channels of one pixel (a free choice: it is just which weight row a lane loads).
+__device__ __forceinline__ int row_wlane(const int l31) { return 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3); }
 
 // ---- shared prologue pieces: the per-channel constants of a lane's 8 channels (one 16-byte slot) and the two transforms ----
 // v & (bit i of bits ? ~0 : 0) on the bit pattern of a float: one signed bit-field extract + one AND (a compare + select pair
@@ -235,6 +265,81 @@ __device__ __forceinline__ void row_side2(const hrp_conv_desc& d, const unsigned
   }
 }
 
+// ---- staging of a strip (conv_row_body, conv_deep_body; R = RowCfg / DeepCfg): piece `wave` of each of the NROWS input rows
+// y0 - 1 .. y0 + TH, 1 KiB by direct-to-LDS DMA - the rows are CONTIGUOUS in NHWC memory, source = row base + lane_off(y), the
+// lane's byte offset inside a row with the LDS swizzle applied (the DMA writes lane-linear, so the permutation goes on the source
+// address); rows outside the image are zero-filled.
+template <class R, class LaneOff>
+__device__ __forceinline__ void row_stage_strip(const char* ximg, char* lds_rows, const int y0, const int H, const int wave, const int lane,
+                                                const LaneOff lane_off) {
+#pragma unroll
+  for (int rs = 0; rs < R::NROWS; ++rs) {
+    const int y = y0 - 1 + rs;
+    char* dst = lds_rows + rs * R::ROWB + wave * 1024;
+    if (y >= 0 && y < H) dma16(ximg + y * (R::W * R::P) + lane_off(y), dst);
+    else *(uint4*)(dst + lane * 16) = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// the zero pixels of a strip tile: one in front of row slot 0, one behind every row slot - the left / right padding, shared by
+// x = W of row r and x = -1 of row r + 1 (C = 256: 11 x 32 slots > 256 threads: two rounds)
+template <class R>
+__device__ __forceinline__ void row_zero_pixels(char* smem, const int tid) {
+  for (int e = tid; e < (R::NROWS + 1) * R::S; e += 256) {
+    const int k = e / R::S, j = e - k * R::S;
+    *(uint4*)(smem + (k == 0 ? 0 : R::P + (k - 1) * R::ROWB + R::W * R::P) + j * 16) = make_uint4(0, 0, 0, 0);
+  }
+}
+
+// ---- the in-place prologue of ONE staged 16-byte vector, pro_mode 2 / 3 (pro_mode 1 is a loop of its own in each body: as a
+// shared helper it cost the launches of that form 0.7 - 1.0 us).  Every lane transforms exactly the bytes it DMA'd itself (no extra
+// barrier).  p: the vector in LDS; off: its byte offset inside x (the same offset addresses pro_x2, pro_side and pro_side2: same
+// geometry; off >> 4 the vector's byte of pro_mask); store: the vector belongs to the rows this workgroup owns (not a halo row of
+// a strip), so its side outputs are written here.  The callers keep what differs between the bodies: which vectors a lane
+// holds, their LDS address / offset, and how many second operands they prefetch into registers at a time.
+// Second operand of pro_mode 2 / 3: the same bytes of pro_x2 (the BatchNorm input resp. the residual) and, where pro_mode 2's
+// ReLU mask comes as bits, the mask byte of the vector (-1: none) - through registers.  ok clear: a vector outside the image.
+template <bool EXT>
+__device__ __forceinline__ void row_pro_operand(const hrp_conv_desc& d, const unsigned off, const bool ok, const bool f3, uint4& x2, int& bits) {
+  x2 = make_uint4(0, 0, 0, 0);
+  bits = -1;
+  if (ok) {
+    x2 = *(const uint4*)((const char*)d.pro_x2 + off);
+    if constexpr (EXT) {
+      if (d.pro_mask && !f3) bits = d.pro_mask[off >> 4];
+    }
+  }
+}
+
+// pro_mode 2 (RowPro::bwd; side outputs pro_side and - written or accumulated - pro_side2) and, f3, pro_mode 3 (RowPro::fwd3; the
+// activation goes to pro_side, its ReLU bits to pro_mask, an OUTPUT here).  f3 / ub / wgm are workgroup-uniform: they select a
+// code version with scalar branches (see RowPro::bwd).
+template <bool EXT>
+__device__ __forceinline__ void row_pro_vec(const hrp_conv_desc& d, const RowPro& pc, char* p, const uint4 x2, const int bits,
+                                            const unsigned off, const bool store, const bool f3, const bool ub, const bool wgm) {
+  if constexpr (EXT) {
+    if (f3) {
+      unsigned ob;
+      const uint4 o3 = pc.fwd3(*(const uint4*)p, x2, ob);
+      *(uint4*)p = o3;
+      if (store) {
+        *(uint4*)((char*)d.pro_side + off) = o3;
+        const_cast<uint8_t*>(d.pro_mask)[off >> 4] = (uint8_t)ob;
+      }
+      return;
+    }
+  }
+  uint4 gm;
+  const uint4 o = pc.template bwd<EXT>(*(const uint4*)p, x2, bits, gm, ub, wgm);
+  *(uint4*)p = o;
+  if (store) {
+    if (d.pro_side) *(uint4*)((char*)d.pro_side + off) = o;
+    if constexpr (EXT) {
+      if (d.pro_side2) row_side2(d, off, gm);
+    }
+  }
+}
+
 // ---- shared epilogue pieces ------------------------------------------------------------------------------------------
 // The lane holds, for each of NT tiles, 16 consecutive output channels (cl .. cl + 15) of one pixel; off[t] = byte offset of
 // those 32 bytes inside y (the same offset addresses res and bnb_x: same geometry).  okmask bit t clear: tile t lies outside
@@ -336,6 +441,12 @@ __device__ __forceinline__ void row_epi_bnb(const hrp_conv_desc& d, const f32x16
   RowEpiOps<NT> e;
   row_epi_load<NT, true, BITS, RES>(d, off, okmask, e);
   row_epi_bnb_math<NT, BITS, RES>(d, acc, off, okmask, cl, ctab, C, e, s1, s2);
+}
+
+// a lane's statistic accumulators (16 channels x two sums) start at zero
+__device__ __forceinline__ void row_zero_sums(float (&s1)[16], float (&s2)[16]) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) s1[i] = s2[i] = 0.f;
 }
 
 template <int NT, bool EXT, bool STATS = true>
@@ -477,14 +588,13 @@ __device__ __forceinline__ void conv_row_body_t(const hrp_conv_desc& d, const Ro
   const int pro = d.pro_mode;
   const bool ub = EXT && d.pro_mask != nullptr, wgm = EXT && d.pro_side2 != nullptr;     // (uniform: RowPro::bwd)
 
-  // ---- weights: A fragments of this wave's 32 output channels.  MFMA row rho = 8 q + 4 h + i carries output channel
-  // 16 h + 4 q + i, so that accumulator register 4 q + i of a lane (half h) is channel 16 h + 4 q + i: consecutive.
+  // ---- weights: A fragments of this wave's 32 output channels (lane -> weight row: row_wlane).
   // C = 64: 144 registers, loaded once per workgroup (one strip).  C = 32: all four waves use the same 18 fragments: they
   // are DMA'd ONCE into LDS (4.5 pieces per wave instead of 18 global loads per wave, whose issue alone was ~1 us of every
   // workgroup) and re-read into registers for every strip's MFMA loop, so that they do not occupy registers during the
   // prologue / epilogue phases of a persistent workgroup.
   bf16x8 wf[9][KS];
-  const int co_lane = m * 32 + 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
+  const int co_lane = m * 32 + row_wlane(l31);
   const char* wl = (const char*)d.w + co_lane * ROW + half * 16;
   char* wlds = smem + R::WLDS_OFF;
   if constexpr (R::PERSIST) {
@@ -510,44 +620,15 @@ __device__ __forceinline__ void conv_row_body_t(const hrp_conv_desc& d, const Ro
   auto stage = [&](int s) {
     int n, y0;
     strip_of(s, n, y0);
-    const char* xg = (const char*)d.x + (unsigned)n * (unsigned)(H * W * P) + lane_off;
-#pragma unroll
-    for (int rs = 0; rs < NROWS; ++rs) {
-      const int y = y0 - 1 + rs;
-      char* dst = lds_rows + rs * ROWB + wave * 1024;
-      if (y >= 0 && y < H) dma16(xg + y * (W * P), dst);
-      else *(uint4*)(dst + lane * 16) = make_uint4(0, 0, 0, 0);
-    }
+    row_stage_strip<R>((const char*)d.x + (unsigned)n * (unsigned)(H * W * P), lds_rows, y0, H, wave, lane, [&](int) { return lane_off; });
   };
   stage(s_begin);
-  // the zero pixels: one in front of row slot 0, one behind every row slot
-  if (tid < (NROWS + 1) * S) {
-    const int k = tid / S, j = tid - k * S;
-    *(uint4*)(smem + (k == 0 ? 0 : P + (k - 1) * ROWB + W * P) + j * 16) = make_uint4(0, 0, 0, 0);
-  }
+  row_zero_pixels<R>(smem, tid);
 
-  // ---- per-channel constants (LDS table [10][C]):
-  //   0 sc, 1 sh        of pro_stats  (prologue 1 / 2: act = fma(x, sc, sh))
-  //   2 a = invstd, 3 b = -mean * invstd, 4 k0, 5 k1     (prologue 2)
-  //   6 a, 7 b, 8 sc, 9 sh   of bnb_stats (epilogue reduce)
+  // ---- per-channel constants (row_ctab_pro / row_ctab_bnb), the two halves on different waves
   const bool bnb = d.bnb_x != nullptr;
-  if (pro != 0 && tid < C) {
-    float mean, inv, sc, sh;
-    row_bn_consts(d.pro_stats, d.pro_gamma, d.pro_beta, d.pro_count, d.pro_eps, tid, C, mean, inv, sc, sh);
-    ctab[0 * C + tid] = sc; ctab[1 * C + tid] = sh;
-    if (pro == 2) {
-      ctab[2 * C + tid] = inv; ctab[3 * C + tid] = -mean * inv;
-      ctab[4 * C + tid] = slot_sum(d.pro_bsums, tid, 2 * C) / d.pro_count;
-      ctab[5 * C + tid] = slot_sum(d.pro_bsums, C + tid, 2 * C) / d.pro_count;
-    }
-  }
-  if (bnb && tid >= 64 && tid < 64 + C) {
-    const int c = tid - 64;
-    float mean, inv, sc, sh;
-    row_bn_consts(d.bnb_stats, d.bnb_gamma, d.bnb_beta, d.bnb_count, d.bnb_eps, c, C, mean, inv, sc, sh);
-    ctab[8 * C + c] = sc; ctab[9 * C + c] = sh;
-    ctab[6 * C + c] = inv; ctab[7 * C + c] = -mean * inv;
-  }
+  if (pro != 0 && tid < C) row_ctab_pro<C>(d, ctab, tid);
+  if (bnb && tid >= 64 && tid < 64 + C) row_ctab_bnb<C>(d, ctab, tid - 64);
   HRP_CSTAMP(1);
   if (pro != 0) __syncthreads();                                          // the constant table
 
@@ -575,8 +656,12 @@ __device__ __forceinline__ void conv_row_body_t(const hrp_conv_desc& d, const Ro
       int cb = lslot * 8;                                       // the lane's 8 channels
       asm volatile("" : "+v"(cb));                              // (opaque per strip: the constants are re-read from LDS, not kept
       pc.load(ctab, C, cb);                                     //  in registers across the MFMA loop of a persistent workgroup)
-      char* side = (char*)d.pro_side;
-      if (pro == 1) {
+      // the vector of row slot rs: its LDS address, its offset in x; rows 1 .. TH are the strip's own
+      auto vec = [&](int rs) { return lds_rows + rs * ROWB + wave * 1024 + lane * 16; };
+      auto off_of = [&](int rs) { return img_off + lane_off + (unsigned)((y0 - 1 + rs) * (W * P)); };
+      auto in_img = [&](int rs) { return y0 - 1 + rs >= 0 && y0 - 1 + rs < H; };
+      if (pro == 1) {      // x' = relu(bn(x)), also stored to pro_side (the activation the weight gradient of this layer reads)
+        char* side = (char*)d.pro_side;
 #pragma unroll
         for (int rs = 0; rs < NROWS; ++rs) {
           const int y = y0 - 1 + rs;
@@ -589,53 +674,17 @@ __device__ __forceinline__ void conv_row_body_t(const hrp_conv_desc& d, const Ro
       } else {
         const bool f3 = EXT && pro == 3;                          // (uniform) block-end forward of the previous block
         if (!f3) pc.load2(ctab, C, cb);
-        // second operand: the same bytes of the BatchNorm input (and the mask byte of the vector), through registers,
-        // five rows at a time
-        const char* x2g = (const char*)d.pro_x2 + img_off + lane_off;
-        const uint8_t* mg = (EXT && d.pro_mask) ? d.pro_mask + ((img_off + lane_off) >> 4) : nullptr;
+        // second operands five rows at a time
 #pragma unroll
         for (int r0 = 0; r0 < NROWS; r0 += 5) {
           uint4 x2[5];
           int bits[5];
 #pragma unroll
-          for (int j = 0; j < 5; ++j) {
-            const int y = y0 - 1 + r0 + j;
-            x2[j] = make_uint4(0, 0, 0, 0);
-            bits[j] = -1;
-            if (y >= 0 && y < H) {
-              x2[j] = *(const uint4*)(x2g + y * (W * P));
-              if constexpr (EXT) {
-                if (mg && !f3) bits[j] = mg[y * (W * P / 16)];
-              }
-            }
-          }
+          for (int j = 0; j < 5; ++j) row_pro_operand<EXT>(d, off_of(r0 + j), in_img(r0 + j), f3, x2[j], bits[j]);
 #pragma unroll
           for (int j = 0; j < 5; ++j) {
-            const int rs = r0 + j, y = y0 - 1 + rs;
-            if (y < 0 || y >= H) continue;
-            char* p = lds_rows + rs * ROWB + wave * 1024 + lane * 16;
-            if constexpr (EXT) {
-              if (f3) {
-                unsigned ob;
-                const uint4 o3 = pc.fwd3(*(const uint4*)p, x2[j], ob);
-                *(uint4*)p = o3;
-                if (rs >= 1 && rs <= TH) {
-                  *(uint4*)(side + img_off + lane_off + y * (W * P)) = o3;
-                  const_cast<uint8_t*>(mg)[y * (W * P / 16)] = (uint8_t)ob;
-                }
-                continue;
-              }
-            }
-            uint4 gm;
-            const uint4 o = pc.template bwd<EXT>(*(const uint4*)p, x2[j], bits[j], gm, ub, wgm);
-            *(uint4*)p = o;
-            if (rs >= 1 && rs <= TH) {
-              const unsigned off = img_off + lane_off + y * (W * P);
-              if (side) *(uint4*)(side + off) = o;
-              if constexpr (EXT) {
-                if (d.pro_side2) row_side2(d, off, gm);
-              }
-            }
+            const int rs = r0 + j;
+            if (in_img(rs)) row_pro_vec<EXT>(d, pc, vec(rs), x2[j], bits[j], off_of(rs), rs >= 1 && rs <= TH, f3, ub, wgm);
           }
         }
       }
@@ -686,8 +735,7 @@ __device__ __forceinline__ void conv_row_body_t(const hrp_conv_desc& d, const Ro
 
     // ---- epilogue: lane = pixel (row y0 + rg*4 + o, x = col*32 + l31), channels m*32 + 16*half .. +15
     float s1[16], s2[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s1[i] = s2[i] = 0.f;
+    row_zero_sums(s1, s2);
     {
       const unsigned out_off = img_off + (unsigned)((y0 + rg * 4) * W + col * 32 + l31) * P + cl * 2;
       constexpr int EG = EXT ? 2 : 4;          // tiles per epilogue group: bounds the registers of the residual / bnb_x rows
@@ -793,42 +841,14 @@ __device__ __forceinline__ void conv_deep_body_t(const hrp_conv_desc& d, const R
   const int px_in_piece = lane / S, pslot = lane % S;
   const int xcol = wave * R::PXP + px_in_piece;
   auto lane_off_of = [&](int y) { return (unsigned)(wave * 1024 + px_in_piece * P + ((pslot ^ R::f(y, xcol)) << 4)); };
-  {
-    const char* xg = (const char*)d.x + img_off;
-#pragma unroll
-    for (int rs = 0; rs < NROWS; ++rs) {
-      const int y = y0 - 1 + rs;
-      char* dst = lds_rows + rs * ROWB + wave * 1024;
-      if (y >= 0 && y < H) dma16(xg + y * (W * P) + lane_off_of(y), dst);
-      else *(uint4*)(dst + lane * 16) = make_uint4(0, 0, 0, 0);
-    }
-  }
-  if (tid < (NROWS + 1) * S) {   // the zero pixels (C = 256: 11 x 32 slots > 256 threads: two rounds)
-    for (int e = tid; e < (NROWS + 1) * S; e += 256) {
-      const int k = e / S, j = e - k * S;
-      *(uint4*)(smem + (k == 0 ? 0 : P + (k - 1) * ROWB + W * P) + j * 16) = make_uint4(0, 0, 0, 0);
-    }
-  }
+  row_stage_strip<R>((const char*)d.x + img_off, lds_rows, y0, H, wave, lane, lane_off_of);
+  row_zero_pixels<R>(smem, tid);
   const bool bnb = d.bnb_x != nullptr;
-  if (pro != 0) {
-    for (int c = tid; c < C; c += 256) {
-      float mean, inv, sc, sh;
-      row_bn_consts(d.pro_stats, d.pro_gamma, d.pro_beta, d.pro_count, d.pro_eps, c, C, mean, inv, sc, sh);
-      ctab[0 * C + c] = sc; ctab[1 * C + c] = sh;
-      if (pro == 2) {
-        ctab[2 * C + c] = inv; ctab[3 * C + c] = -mean * inv;
-        ctab[4 * C + c] = slot_sum(d.pro_bsums, c, 2 * C) / d.pro_count;
-        ctab[5 * C + c] = slot_sum(d.pro_bsums, C + c, 2 * C) / d.pro_count;
-      }
-    }
+  if (pro != 0) {      // per-channel constants (row_ctab_pro / row_ctab_bnb)
+    for (int c = tid; c < C; c += 256) row_ctab_pro<C>(d, ctab, c);
   }
   if (bnb) {
-    for (int c = tid; c < C; c += 256) {
-      float mean, inv, sc, sh;
-      row_bn_consts(d.bnb_stats, d.bnb_gamma, d.bnb_beta, d.bnb_count, d.bnb_eps, c, C, mean, inv, sc, sh);
-      ctab[8 * C + c] = sc; ctab[9 * C + c] = sh;
-      ctab[6 * C + c] = inv; ctab[7 * C + c] = -mean * inv;
-    }
+    for (int c = tid; c < C; c += 256) row_ctab_bnb<C>(d, ctab, c);
   }
   HRP_CSTAMP(1);
 
@@ -836,14 +856,18 @@ __device__ __forceinline__ void conv_deep_body_t(const hrp_conv_desc& d, const R
   if (pro != 0) {
     __syncthreads();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    char* side = (char*)d.pro_side;
     constexpr int NPAR = C == 256 ? 2 : 1;
+    auto vec = [&](int rs) { return lds_rows + rs * ROWB + wave * 1024 + lane * 16; };
+    auto off_of = [&](int rs) { const int y = y0 - 1 + rs; return img_off + (unsigned)(y * (W * P)) + lane_off_of(y); };
 #pragma unroll
     for (int par = 0; par < NPAR; ++par) {
       RowPro pc;
       const int cb = (pslot ^ R::f(par, xcol)) * 8;               // f depends on y only through its parity (W = 8) or not at all
       pc.load(ctab, C, cb);
+      // this parity's rows inside the image
+      auto mine = [&](int rs) { const int y = y0 - 1 + rs; return y >= 0 && y < H && !(NPAR == 2 && ((y & 1) != par)); };
       if (pro == 1) {
+        char* side = (char*)d.pro_side;
 #pragma unroll
         for (int rs = 0; rs < NROWS; ++rs) {
           const int y = y0 - 1 + rs;
@@ -856,51 +880,14 @@ __device__ __forceinline__ void conv_deep_body_t(const hrp_conv_desc& d, const R
       } else {
         const bool f3 = EXT && pro == 3;                          // (uniform) block-end forward of the previous block
         if (!f3) pc.load2(ctab, C, cb);
-        // the BatchNorm inputs (and mask bytes) of this parity's rows: same lane-constant addressing, through registers
+        // second operands of all of this parity's rows at once
         uint4 x2[NROWS];
         int bits[NROWS];
 #pragma unroll
-        for (int rs = 0; rs < NROWS; ++rs) {
-          const int y = y0 - 1 + rs;
-          x2[rs] = make_uint4(0, 0, 0, 0);
-          bits[rs] = -1;
-          if (y >= 0 && y < H && !(NPAR == 2 && ((y & 1) != par))) {
-            const unsigned off = img_off + y * (W * P) + lane_off_of(y);
-            x2[rs] = *(const uint4*)((const char*)d.pro_x2 + off);
-            if constexpr (EXT) {
-              if (d.pro_mask && !f3) bits[rs] = d.pro_mask[off >> 4];
-            }
-          }
-        }
+        for (int rs = 0; rs < NROWS; ++rs) row_pro_operand<EXT>(d, off_of(rs), mine(rs), f3, x2[rs], bits[rs]);
 #pragma unroll
-        for (int rs = 0; rs < NROWS; ++rs) {
-          const int y = y0 - 1 + rs;
-          if (y < 0 || y >= H || (NPAR == 2 && ((y & 1) != par))) continue;
-          char* p = lds_rows + rs * ROWB + wave * 1024 + lane * 16;
-          if constexpr (EXT) {
-            if (f3) {
-              unsigned ob;
-              const uint4 o3 = pc.fwd3(*(const uint4*)p, x2[rs], ob);
-              *(uint4*)p = o3;
-              if (rs >= 1 && rs <= TH) {
-                const unsigned off = img_off + y * (W * P) + lane_off_of(y);
-                *(uint4*)(side + off) = o3;
-                const_cast<uint8_t*>(d.pro_mask)[off >> 4] = (uint8_t)ob;
-              }
-              continue;
-            }
-          }
-          uint4 gm;
-          const uint4 o = pc.template bwd<EXT>(*(const uint4*)p, x2[rs], bits[rs], gm, ub, wgm);
-          *(uint4*)p = o;
-          if (rs >= 1 && rs <= TH) {
-            const unsigned off = img_off + y * (W * P) + lane_off_of(y);
-            if (side) *(uint4*)(side + off) = o;
-            if constexpr (EXT) {
-              if (d.pro_side2) row_side2(d, off, gm);
-            }
-          }
-        }
+        for (int rs = 0; rs < NROWS; ++rs)
+          if (mine(rs)) row_pro_vec<EXT>(d, pc, vec(rs), x2[rs], bits[rs], off_of(rs), rs >= 1 && rs <= TH, f3, ub, wgm);
       }
     }
   } else {
@@ -919,9 +906,7 @@ __device__ __forceinline__ void conv_deep_body_t(const hrp_conv_desc& d, const R
       for (int i = 0; i < 16; ++i) acc[mi][t][i] = 0.f;
   {
     const int r = l31 / W, x = l31 % W;
-    // weight rows of the lane (MFMA row rho = l31 carries channel 16 h + 4 q + i of the block, see conv_row_body)
-    const int co_l = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
-    const char* wl = (const char*)d.w + (size_t)((wave * MW) * 32 + co_l) * ROW + half * 16;
+    const char* wl = (const char*)d.w + (size_t)((wave * MW) * 32 + row_wlane(l31)) * ROW + half * 16;
     auto wload = [&](int kk, bf16x8 (&wb)[MW][9]) {
 #pragma unroll
       for (int mi = 0; mi < MW; ++mi)
@@ -990,8 +975,7 @@ __device__ __forceinline__ void conv_deep_body_t(const hrp_conv_desc& d, const R
 #pragma unroll
     for (int t = 0; t < NW; ++t) off[t] = pix_off + cl * 2 + t * (RPT * W * P);
     float s1[16], s2[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s1[i] = s2[i] = 0.f;
+    row_zero_sums(s1, s2);
     row_epilogue<NW, EXT>(d, acc[mi], off, (1u << NW) - 1, cl, ctab, C, bnb, s1, s2);
     if (d.stats) row_stats_commit(d, row_reduce32(s1, s2, l31), l31, cl, ctab, C, bnb, stat_slot);
   }
@@ -1081,25 +1065,11 @@ __device__ __forceinline__ void conv_img_body_t(const hrp_conv_desc& d, const Ro
     *(uint4*)(smem + k * T + 32 * P + j * 16) = make_uint4(0, 0, 0, 0);
   }
   const bool bnb = d.bnb_x != nullptr;
-  if (pro != 0) {
-    for (int c = tid; c < C; c += 256) {
-      float mean, inv, sc, sh;
-      row_bn_consts(d.pro_stats, d.pro_gamma, d.pro_beta, d.pro_count, d.pro_eps, c, C, mean, inv, sc, sh);
-      ctab[0 * C + c] = sc; ctab[1 * C + c] = sh;
-      if (pro == 2) {
-        ctab[2 * C + c] = inv; ctab[3 * C + c] = -mean * inv;
-        ctab[4 * C + c] = slot_sum(d.pro_bsums, c, 2 * C) / d.pro_count;
-        ctab[5 * C + c] = slot_sum(d.pro_bsums, C + c, 2 * C) / d.pro_count;
-      }
-    }
+  if (pro != 0) {      // per-channel constants (row_ctab_pro / row_ctab_bnb)
+    for (int c = tid; c < C; c += 256) row_ctab_pro<C>(d, ctab, c);
   }
   if (bnb) {
-    for (int c = tid; c < C; c += 256) {
-      float mean, inv, sc, sh;
-      row_bn_consts(d.bnb_stats, d.bnb_gamma, d.bnb_beta, d.bnb_count, d.bnb_eps, c, C, mean, inv, sc, sh);
-      ctab[8 * C + c] = sc; ctab[9 * C + c] = sh;
-      ctab[6 * C + c] = inv; ctab[7 * C + c] = -mean * inv;
-    }
+    for (int c = tid; c < C; c += 256) row_ctab_bnb<C>(d, ctab, c);
   }
   HRP_CSTAMP(1);
 
@@ -1108,7 +1078,10 @@ __device__ __forceinline__ void conv_img_body_t(const hrp_conv_desc& d, const Ro
   if (pro != 0) {
     __syncthreads();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    char* side = (char*)d.pro_side;
+    // the vector of the wave's piece i: its LDS address, its offset in x; pieces of images outside the batch are skipped
+    auto vec = [&](int i) { const int q = wave + 4 * i; return smem + (q / PPT) * T + (q % PPT) * 1024 + lane * 16; };
+    auto off_of = [&](int i) { return grp_off + piece_off(i); };
+    auto valid = [&](int i) { return (wave + 4 * i) / PPT < nvalid * TPI; };
 #pragma unroll
     for (int hsel = 0; hsel < 2; ++hsel) {
       // C = 128: pieces i = 8 hsel .. 8 hsel + 7; C = 256: pieces of parity hsel (i = hsel, hsel + 2, ...)
@@ -1117,6 +1090,7 @@ __device__ __forceinline__ void conv_img_body_t(const hrp_conv_desc& d, const Ro
       const int cb = lslot_of(piece_i(0)) * 8;
       pc.load(ctab, C, cb);
       if (pro == 1) {
+        char* side = (char*)d.pro_side;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int i = piece_i(j), q = wave + 4 * i, tq = q / PPT;
@@ -1132,43 +1106,10 @@ __device__ __forceinline__ void conv_img_body_t(const hrp_conv_desc& d, const Ro
         uint4 x2[8];
         int bits[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int i = piece_i(j), q = wave + 4 * i;
-          x2[j] = make_uint4(0, 0, 0, 0);
-          bits[j] = -1;
-          if (q / PPT < nvalid * TPI) {
-            const unsigned off = grp_off + piece_off(i);
-            x2[j] = *(const uint4*)((const char*)d.pro_x2 + off);
-            if constexpr (EXT) {
-              if (d.pro_mask && !f3) bits[j] = d.pro_mask[off >> 4];
-            }
-          }
-        }
+        for (int j = 0; j < 8; ++j) row_pro_operand<EXT>(d, off_of(piece_i(j)), valid(piece_i(j)), f3, x2[j], bits[j]);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const int i = piece_i(j), q = wave + 4 * i, tq = q / PPT;
-          if (tq >= nvalid * TPI) continue;
-          char* p = smem + tq * T + (q % PPT) * 1024 + lane * 16;
-          if constexpr (EXT) {
-            if (f3) {
-              unsigned ob;
-              const uint4 o3 = pc.fwd3(*(const uint4*)p, x2[j], ob);
-              *(uint4*)p = o3;
-              const unsigned off = grp_off + piece_off(i);
-              *(uint4*)(side + off) = o3;
-              const_cast<uint8_t*>(d.pro_mask)[off >> 4] = (uint8_t)ob;
-              continue;
-            }
-          }
-          uint4 gm;
-          const uint4 o = pc.template bwd<EXT>(*(const uint4*)p, x2[j], bits[j], gm, ub, wgm);
-          *(uint4*)p = o;
-          const unsigned off = grp_off + piece_off(i);
-          if (side) *(uint4*)(side + off) = o;
-          if constexpr (EXT) {
-            if (d.pro_side2) row_side2(d, off, gm);
-          }
-        }
+        for (int j = 0; j < 8; ++j)
+          if (valid(piece_i(j))) row_pro_vec<EXT>(d, pc, vec(piece_i(j)), x2[j], bits[j], off_of(piece_i(j)), true, f3, ub, wgm);
       }
     }
   } else {
@@ -1185,8 +1126,7 @@ __device__ __forceinline__ void conv_img_body_t(const hrp_conv_desc& d, const Ro
     for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
   {
     const int r = l31 / W, x = l31 % W;
-    const int co_l = 16 * ((l31 >> 2) & 1) + 4 * (l31 >> 3) + (l31 & 3);
-    const char* wl = (const char*)d.w + (size_t)(cbk * 128 + wave * 32 + co_l) * ROW + half * 16;
+    const char* wl = (const char*)d.w + (size_t)(cbk * 128 + wave * 32 + row_wlane(l31)) * ROW + half * 16;
     // weights stream through registers in groups of GT taps, NBUF groups in flight (C = 128: the three taps of one
     // kernel row, 3 buffers - 128 accumulator registers leave no room for two 9-tap buffers; C = 256: all 9 taps, 2 buffers)
     constexpr int GT = C == 128 ? 3 : 9, NG = 9 / GT, NBUF = C == 128 ? 3 : 2;
@@ -1262,8 +1202,7 @@ __device__ __forceinline__ void conv_img_body_t(const hrp_conv_desc& d, const Ro
     const int cl = cbk * 128 + wave * 32 + 16 * half;
     const unsigned pix0 = grp_off + (unsigned)l31 * P + cl * 2;
     float s1[16], s2[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s1[i] = s2[i] = 0.f;
+    row_zero_sums(s1, s2);
     constexpr int EG = NT == 8 ? 2 : 4;       // tiles per epilogue group: bounds the registers of the residual / bnb_x rows
 #pragma unroll
     for (int t0 = 0; t0 < NT; t0 += EG) {
@@ -1289,14 +1228,21 @@ __global__ __launch_bounds__(256, 2) void conv_img_kernel(const hrp_conv_desc d,
   conv_img_body<C>(d, rp, blockIdx.x, blockIdx.x & (HRP_STAT_SLOTS - 1));
 }
 
-// workgroups of a planned problem
-static inline int row_grid(const RowPlan& rp, int C) {
-  return (C <= 64 && !rp.img) ? (rp.nstrips + rp.spw - 1) / rp.spw : rp.nstrips;
-}
+// Host: the variant that runs a planned problem - the ONE place that maps (C, rp.img) to a kernel.  cfg is the kernel id of
+// ConvProblem::cfg (conv_batch.h): 5 / 6 conv_row_body<32 / 64>, 7 / 8 conv_deep_body<128 / 256>, 9 / 10 conv_img_body<128 / 256>.
+struct RowVariant {
+  int cfg, lds_bytes, grid;      // kernel id; dynamic LDS; workgroups
+};
 
-static inline int row_lds_bytes(int C, int img) {
-  if (img) return C == 128 ? ImgCfg<128>::LDS_BYTES : ImgCfg<256>::LDS_BYTES;
-  return C == 32 ? RowCfg<32>::LDS_BYTES : C == 64 ? RowCfg<64>::LDS_BYTES : C == 128 ? DeepCfg<128>::LDS_BYTES : DeepCfg<256>::LDS_BYTES;
+static inline RowVariant row_variant(const int C, const RowPlan& rp) {
+  const int groups = (rp.nstrips + rp.spw - 1) / rp.spw;      // persistent workgroups of the 32 / 64-channel kernel
+  if (rp.img) return C == 128 ? RowVariant{9, ImgCfg<128>::LDS_BYTES, rp.nstrips} : RowVariant{10, ImgCfg<256>::LDS_BYTES, rp.nstrips};
+  switch (C) {
+    case 32: return RowVariant{5, RowCfg<32>::LDS_BYTES, groups};
+    case 64: return RowVariant{6, RowCfg<64>::LDS_BYTES, groups};
+    case 128: return RowVariant{7, DeepCfg<128>::LDS_BYTES, rp.nstrips};
+    default: return RowVariant{8, DeepCfg<256>::LDS_BYTES, rp.nstrips};
+  }
 }
 
 // -> HRP_OK when launched, -100 when the problem is not a row-strip problem
@@ -1307,26 +1253,22 @@ static int launch_conv_row(const hrp_conv_desc& d, hipStream_t s) {
   row_plan(d, rp);
   // a 128-channel layer launched ALONE (inference plans: the third branch's convolutions have no batch partner) takes the
   // half-image variant: 2 N workgroups instead of N - at B = 64 the whole-image kernel occupies a quarter of the chip
-  // (forward_only 7.255 -> 7.17 ms).  Inside a batch the whole-image form stays (the other problems fill the chip).
+  // (forward_only 7.255 -> 7.17 ms).  Inside a batch (conv_batch_plan_one) the whole-image form stays: the other problems
+  // fill the chip.
   if (rp.img && C == 128) { rp.img = 0; rp.nstrips = d.N * rp.spi; }
-  if (C == 32) hipLaunchKernelGGL(conv_row_kernel<32>, dim3(row_grid(rp, 32)), dim3(256), RowCfg<32>::LDS_BYTES, s, d, rp);
-  else if (C == 64) hipLaunchKernelGGL(conv_row_kernel<64>, dim3(row_grid(rp, 64)), dim3(256), RowCfg<64>::LDS_BYTES, s, d, rp);
-  else if (rp.img) {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)conv_img_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)conv_img_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr = true;
-    }
-    if (C == 128) hipLaunchKernelGGL(conv_img_kernel<128>, dim3(rp.nstrips), dim3(256), ImgCfg<128>::LDS_BYTES, s, d, rp);
-    else hipLaunchKernelGGL(conv_img_kernel<256>, dim3(rp.nstrips), dim3(256), ImgCfg<256>::LDS_BYTES, s, d, rp);
+  // the single-problem kernels in the order of row_variant's cfg ids 5 .. 10; one that needs more LDS than a kernel gets without
+  // asking is registered at its first launch
+  using Kernel = void (*)(const hrp_conv_desc, const RowPlan);
+  static const Kernel kernels[6] = {conv_row_kernel<32>, conv_row_kernel<64>, conv_deep_kernel<128>,
+                                    conv_deep_kernel<256>, conv_img_kernel<128>, conv_img_kernel<256>};
+  static bool attr[6];
+  const RowVariant v = row_variant(C, rp);
+  const int k = v.cfg - 5;
+  if (v.lds_bytes > 64 * 1024 && !attr[k]) {
+    (void)hipFuncSetAttribute((const void*)kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr[k] = true;
   }
-  else if (C == 128) hipLaunchKernelGGL(conv_deep_kernel<128>, dim3(rp.nstrips), dim3(256), DeepCfg<128>::LDS_BYTES, s, d, rp);
-  else {
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)conv_deep_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    hipLaunchKernelGGL(conv_deep_kernel<256>, dim3(rp.nstrips), dim3(256), DeepCfg<256>::LDS_BYTES, s, d, rp);
-  }
+  hipLaunchKernelGGL(kernels[k], dim3(v.grid), dim3(256), v.lds_bytes, s, d, rp);
   return check_launch("conv_row_kernel");
 }
 

@@ -472,6 +472,136 @@ def test_rowconv_in_a_batched_launch_equals_single_launches():
         assert torch.equal(y, s)
 
 
+FUSED_FORMS = ["pro1_side", "pro2", "pro2_mask_side2", "pro3", "bnb", "bnb_mask"]
+
+
+def fused_form_problem(nv, form, Cc, N, H, g, acc2=0):
+    """One row-strip problem of a fused form on random operands, set up as the single-launch test of that form does.
+    -> (descriptor, {name: output tensor}, statistic slots, tensors to keep alive).  The outputs hold their initial contents
+    (res == y accumulates, pro_side2 may): a caller that launches twice restores them in between."""
+    W = 2048 // Cc
+    n = N * H * W * Cc
+
+    def rnd(scale=1.0, shift=0.0):
+        return bf(torch.randn(N, Cc, H, W, generator=g) * scale + shift)
+
+    def bn_of(x):
+        gamma, beta = torch.rand(Cc, generator=g) + 0.5, torch.randn(Cc, generator=g) * 0.3
+        _, _, _, _, tot, cnt = bn_consts(x, gamma, beta)
+        return slots_of(tot, g), gamma.to(DEV), beta.to(DEV), float(cnt)
+
+    x, x2 = rnd(1.5, 0.3), rnd(2.0, 0.2)
+    w = bf(torch.randn(Cc, Cc, 3, 3, generator=g) / np.sqrt(9 * Cc))
+    wp, wpt = pack(nv, w)
+    xd, x2d = nhwc(x), nhwc(x2)
+    y = nhwc(rnd())
+    st = torch.zeros(SLOTS * 2 * Cc, dtype=torch.float64, device=DEV)
+    side = torch.full((n,), 7.0, dtype=torch.bfloat16, device=DEV)
+    outs, keep = {"y": y}, [xd, x2d, wp, wpt]
+    d = desc(nv, xd, wp if form in ("pro1_side", "pro3") else wpt, y, N, H, W, Cc, transposed=form not in ("pro1_side", "pro3"))
+    d.stats = st.data_ptr()
+
+    def prologue(mode, stats_of):
+        ps, gd, bd, cnt = bn_of(stats_of)
+        d.pro_mode, d.pro_stats, d.pro_gamma, d.pro_beta, d.pro_count, d.pro_eps = mode, ps.data_ptr(), gd.data_ptr(), bd.data_ptr(), cnt, EPS
+        d.pro_side = side.data_ptr()
+        outs["pro_side"] = side
+        keep.extend([ps, gd, bd])
+        if mode >= 2:
+            d.pro_x2 = x2d.data_ptr()
+        if mode == 2:       # the sums a reduce pass would have left: any per-channel totals of the right size
+            bs = slots_of(torch.randn(2 * Cc, generator=g) * float(N * H * W) ** 0.5, g)
+            d.pro_bsums = bs.data_ptr()
+            keep.append(bs)
+
+    def reduce_epilogue(with_mask):
+        bx = rnd(2.0, -0.4)
+        bxd = nhwc(bx)
+        ps, gd, bd, cnt = bn_of(bx)
+        d.bnb_x, d.bnb_x_pitch = bxd.data_ptr(), Cc
+        d.bnb_stats, d.bnb_gamma, d.bnb_beta, d.bnb_count, d.bnb_eps = ps.data_ptr(), gd.data_ptr(), bd.data_ptr(), cnt, EPS
+        keep.extend([bxd, ps, gd, bd])
+        if with_mask:
+            mk = mask_bits(torch.rand(N, Cc, H, W, generator=g) > 0.4)
+            d.bnb_mask, d.bnb_mask_pitch = mk.data_ptr(), Cc // 8
+            keep.append(mk)
+
+    if form == "pro1_side":
+        prologue(1, x)
+    elif form == "pro2":                  # (test_rowconv_bn_backward_apply_prologue: accumulated onto an existing gradient)
+        prologue(2, x2)
+        d.res = y.data_ptr()
+    elif form == "pro2_mask_side2":       # (test_rowconv_block_end_apply_prologue)
+        prologue(2, x2)
+        mk = mask_bits(torch.rand(N, Cc, H, W, generator=g) > 0.45)
+        side2 = nhwc(rnd())
+        d.pro_mask, d.pro_side2, d.pro_side2_acc = mk.data_ptr(), side2.data_ptr(), acc2
+        outs["pro_side2"] = side2
+        keep.append(mk)
+        reduce_epilogue(False)
+    elif form == "pro3":                  # (test_rowconv_block_end_prologue)
+        prologue(3, x)
+        mask = torch.full((n // 8,), 0xAA, dtype=torch.uint8, device=DEV)
+        d.pro_mask = mask.data_ptr()
+        outs["pro_mask"] = mask
+    elif form == "bnb":                   # (test_rowconv_bn_backward_reduce_epilogue)
+        reduce_epilogue(False)
+    elif form == "bnb_mask":              # (test_rowconv_block_end_reduce_epilogue)
+        prologue(2, x2)
+        d.res = y.data_ptr()
+        reduce_epilogue(True)
+    else:
+        raise ValueError(form)
+    assert nv.lib().hrp_conv_rowstrip_channels(C.byref(d)) == Cc
+    return d, outs, st, keep
+
+
+@pytest.mark.parametrize("form", FUSED_FORMS)
+def test_rowconv_fused_forms_in_a_batched_launch_equal_single_launches(form):
+    """The fused forms (BatchNorm prologues 1 / 2 / 3 with their side and mask outputs, the epilogue reduce with and without a bit
+    mask) of a 128-, a 256- and a 32-channel problem in ONE HRP_BATCH_CONV launch against their single launches.  A 128-channel
+    problem launched alone runs the strip kernel (conv_deep_body), inside a batch the whole-image kernel (conv_img_body<128>): this is
+    the kernel-level test of that body's prologue and epilogue.  y, the side outputs and the mask bytes bit for bit; the statistic
+    slots summed, to 2e-3 (their fp64 atomics - and the fp32 partial sums of differently shaped workgroups - have no fixed order)."""
+    nv = nvmod()
+    g = torch.Generator().manual_seed(7 + FUSED_FORMS.index(form))
+    probs = [fused_form_problem(nv, form, Cc, N, H, g, acc2=k & 1) for k, (Cc, N, H) in enumerate([(128, 2, 16), (256, 3, 8), (32, 2, 64)])]
+    init = [({k: v.clone() for k, v in outs.items()}) for _, outs, _, _ in probs]
+
+    def reset():
+        for (_, outs, st, _), i0 in zip(probs, init):
+            for k, v in outs.items():
+                v.copy_(i0[k])
+            st.zero_()
+
+    def snapshot():
+        torch.cuda.synchronize()
+        return [({k: v.clone() for k, v in outs.items()}, st.view(SLOTS, -1).sum(0).cpu()) for _, outs, st, _ in probs]
+
+    for d, _, _, _ in probs:
+        nv.call("hrp_conv2d_fwd", C.byref(d), None)
+    single = snapshot()
+    reset()
+    n = len(probs)
+    arr = (nv.ConvDesc * n)(*[p[0] for p in probs])
+    info = nv.BatchInfo()
+    nb = int(nv.lib().hrp_batch_table_bytes(nv.BATCH_CONV, n))
+    host = (C.c_char * nb)()
+    nv.check(nv.lib().hrp_batch_prepare(nv.BATCH_CONV, arr, n, host, C.byref(info)), "prepare")
+    # the plan really holds the whole-image body: one workgroup per image of the 128-channel problem (as strips: N H / 8 = 4),
+    # 2 x 2 for three 256-channel images, 16 strips of the 32-channel one
+    assert sorted(info.blk0[k + 1] - info.blk0[k] for k in range(n)) == [2, 4, 16], list(info.blk0[:n + 1])
+    table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(DEV)
+    nv.check(nv.lib().hrp_batch_launch(table.data_ptr(), C.byref(info), None), "launch")
+    batched = snapshot()
+    for (so, ss), (bo, bs), i0 in zip(single, batched, init):
+        for k in so:
+            assert not torch.equal(so[k], i0[k]), (k, "the launch wrote nothing")
+            assert torch.equal(bo[k], so[k]), k
+        assert ss.abs().max() > 0
+        assert rel(bs, ss) < 2e-3, rel(bs, ss)
+
+
 @pytest.mark.parametrize("Cc", [32, 64, 128, 256])
 def test_fused_basic_block_equals_elementwise_path(Cc):
     """A train-mode bf16 BasicBlock (HRnet.py:28-57) with its interior BatchNorm + ReLU inside the row-strip convolutions
