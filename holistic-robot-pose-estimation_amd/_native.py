@@ -187,6 +187,11 @@ class OptChunk(C.Structure):
     _fields_ = [("tensor", C.c_int32), ("offset", C.c_int32)]
 
 
+class OptGroup(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("reserved", C.c_float * 3)]
+
+
 class RegStepDesc(C.Structure):
     """hrp_regressor_step_desc (include/hrp.h): one step of one iterative regressor."""
     _fields_ = [("M", C.c_int32), ("P", C.c_int32), ("K", C.c_int32), ("N", C.c_int32),
@@ -295,6 +300,8 @@ PROTOTYPES = {
     "hrp_mul_f32": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
     "hrp_opt_grad_sumsq": [_P, _P, _I, _P, _P, _P],
     "hrp_opt_adam_step": [_P, _P, _I, _P, _F, _P, _F, _F, _F, _F, _P],
+    "hrp_opt_adam_step_groups": [_P, _P, _I, _P, _F, _P, _P, _I, _P, _P],
+    "hrp_opt_set_group": [_P, _I, _I, _F, _F, _F, _F, _F, _P],
     "hrp_grad_accumulate": [_P, _P, _L, _I, _F, _P],
     "hrp_batch_prepare": [_I, _P, _I, _P, C.POINTER(BatchInfo)],
     "hrp_batch_launch": [_P, C.POINTER(BatchInfo), _P],

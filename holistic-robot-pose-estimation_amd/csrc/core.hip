@@ -765,13 +765,13 @@ __global__ __launch_bounds__(256) void opt_fold_sumsq_kernel(const float* __rest
   if (threadIdx.x < HRP_STAT_SLOTS) slots[threadIdx.x] = threadIdx.x == 0 ? part[0] : 0.f;
 }
 
-__global__ __launch_bounds__(256) void opt_adam_kernel(const hrp_opt_tensor* __restrict__ tensors,
-                                                       const hrp_opt_chunk* __restrict__ chunks,
-                                                       const float* __restrict__ slots, float max_norm,
-                                                       const float* __restrict__ step_dev, float lr, float b1, float b2,
-                                                       float eps) {
-  const hrp_opt_chunk ck = chunks[blockIdx.x];
-  const hrp_opt_tensor t = tensors[ck.tensor];
+// One chunk of the clipped Adam step, shared by the two kernels below.  DECAY = false is hrp_opt_adam_step's arithmetic; DECAY = true
+// adds torch.optim.Adam's L2 term where wd != 0: the moments see g + wd * p (p before the update, already in registers), the
+// gradient written back is the clipped one without it.
+template <bool DECAY>
+__device__ __forceinline__ void opt_adam_chunk(const hrp_opt_tensor t, const hrp_opt_chunk ck, const float* __restrict__ slots,
+                                               float max_norm, const float* __restrict__ step_dev, float lr, float b1, float b2,
+                                               float eps, float wd) {
   const int64_t base = (int64_t)ck.offset * HRP_OPT_CHUNK;
   const int64_t left = t.numel - base;
   const int n = left < HRP_OPT_CHUNK ? (int)left : HRP_OPT_CHUNK;
@@ -789,21 +789,64 @@ __global__ __launch_bounds__(256) void opt_adam_kernel(const hrp_opt_tensor* __r
   float* g = t.grad + base;
   float* m = t.exp_avg + base;
   float* v = t.exp_avg_sq + base;
-  auto upd = [&](float& pp, float& gg, float& mm, float& vv) {
-    gg *= clip;
-    mm = b1 * mm + (1.f - b1) * gg;
-    vv = b2 * vv + (1.f - b2) * gg * gg;
-    pp -= step_size * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);
-  };
-  if ((n & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) {
-    for (int i = threadIdx.x * 4; i < n; i += 1024) {
-      float4 pp = *(float4*)(p + i), gg = *(float4*)(g + i), mm = *(float4*)(m + i), vv = *(float4*)(v + i);
-      upd(pp.x, gg.x, mm.x, vv.x); upd(pp.y, gg.y, mm.y, vv.y); upd(pp.z, gg.z, mm.z, vv.z); upd(pp.w, gg.w, mm.w, vv.w);
-      *(float4*)(p + i) = pp; *(float4*)(g + i) = gg; *(float4*)(m + i) = mm; *(float4*)(v + i) = vv;
+  // (the branch is uniform over the launch's group; each side is its own loop so that wd == 0 runs the DECAY = false instructions)
+  auto run = [&](auto with_decay) {
+    auto upd = [&](float& pp, float& gg, float& mm, float& vv) {
+      gg *= clip;
+      if constexpr (decltype(with_decay)::value) {
+        const float ge = gg + wd * pp;
+        mm = b1 * mm + (1.f - b1) * ge;
+        vv = b2 * vv + (1.f - b2) * ge * ge;
+      } else {
+        mm = b1 * mm + (1.f - b1) * gg;
+        vv = b2 * vv + (1.f - b2) * gg * gg;
+      }
+      pp -= step_size * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);
+    };
+    if ((n & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) {
+      for (int i = threadIdx.x * 4; i < n; i += 1024) {
+        float4 pp = *(float4*)(p + i), gg = *(float4*)(g + i), mm = *(float4*)(m + i), vv = *(float4*)(v + i);
+        upd(pp.x, gg.x, mm.x, vv.x); upd(pp.y, gg.y, mm.y, vv.y); upd(pp.z, gg.z, mm.z, vv.z); upd(pp.w, gg.w, mm.w, vv.w);
+        *(float4*)(p + i) = pp; *(float4*)(g + i) = gg; *(float4*)(m + i) = mm; *(float4*)(v + i) = vv;
+      }
+    } else {
+      for (int i = threadIdx.x; i < n; i += 256) upd(p[i], g[i], m[i], v[i]);
     }
-  } else {
-    for (int i = threadIdx.x; i < n; i += 256) upd(p[i], g[i], m[i], v[i]);
-  }
+  };
+  if (DECAY && wd != 0.f) run(std::true_type{});
+  else run(std::false_type{});
+}
+
+__global__ __launch_bounds__(256) void opt_adam_kernel(const hrp_opt_tensor* __restrict__ tensors,
+                                                       const hrp_opt_chunk* __restrict__ chunks,
+                                                       const float* __restrict__ slots, float max_norm,
+                                                       const float* __restrict__ step_dev, float lr, float b1, float b2,
+                                                       float eps) {
+  const hrp_opt_chunk ck = chunks[blockIdx.x];
+  const hrp_opt_tensor t = tensors[ck.tensor];
+  opt_adam_chunk<false>(t, ck, slots, max_norm, step_dev, lr, b1, b2, eps, 0.f);
+}
+
+// The hyper-parameters come from the group table at run time (uniform per workgroup: one index and five floats per chunk), so a
+// replayed HIP graph applies what hrp_opt_set_group wrote last.  An index outside the table is clamped: no read out of bounds.
+__global__ __launch_bounds__(256) void opt_adam_groups_kernel(const hrp_opt_tensor* __restrict__ tensors,
+                                                              const hrp_opt_chunk* __restrict__ chunks,
+                                                              const float* __restrict__ slots, float max_norm,
+                                                              const float* __restrict__ step_dev,
+                                                              const hrp_opt_group* __restrict__ groups, int ngroups,
+                                                              const int32_t* __restrict__ tensor_group) {
+  const hrp_opt_chunk ck = chunks[blockIdx.x];
+  const int gi = tensor_group[ck.tensor];
+  const hrp_opt_group h = groups[gi < 0 ? 0 : gi >= ngroups ? ngroups - 1 : gi];
+  opt_adam_chunk<true>(tensors[ck.tensor], ck, slots, max_norm, step_dev, h.lr, h.beta1, h.beta2, h.eps, h.weight_decay);
+}
+
+// one thread, plain stores: the values travel as launch arguments (nothing on the host to overwrite while a launch is queued)
+__global__ void opt_set_group_kernel(hrp_opt_group* __restrict__ groups, int index, float lr, float b1, float b2, float eps,
+                                     float wd) {
+  hrp_opt_group h = {};
+  h.lr = lr, h.beta1 = b1, h.beta2 = b2, h.eps = eps, h.weight_decay = wd;
+  groups[index] = h;
 }
 
 extern "C" int hrp_opt_grad_sumsq(const hrp_opt_tensor* tensors_dev, const hrp_opt_chunk* chunks_dev, int nchunks,
@@ -823,6 +866,28 @@ extern "C" int hrp_opt_adam_step(const hrp_opt_tensor* tensors_dev, const hrp_op
   hipLaunchKernelGGL(opt_adam_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, tensors_dev, chunks_dev, sumsq_slots,
                      max_norm, step_dev, lr, beta1, beta2, eps);
   return check_launch("opt_adam_step");
+}
+
+extern "C" int hrp_opt_adam_step_groups(const hrp_opt_tensor* tensors_dev, const hrp_opt_chunk* chunks_dev, int nchunks,
+                                        const float* sumsq_slots, float max_norm, const float* step_dev,
+                                        const hrp_opt_group* groups_dev, int ngroups, const int32_t* tensor_group_dev,
+                                        void* stream) {
+  HRP_REQUIRE(tensors_dev && chunks_dev && step_dev && nchunks > 0, "opt_adam_step_groups: bad args");
+  HRP_REQUIRE(groups_dev && tensor_group_dev, "opt_adam_step_groups: null group table");
+  HRP_REQUIRE(ngroups >= 1, "opt_adam_step_groups: ngroups %d < 1", ngroups);
+  HRP_REQUIRE(max_norm <= 0.f || sumsq_slots, "opt_adam_step_groups: clipping needs the sum-of-squares slots");
+  hipLaunchKernelGGL(opt_adam_groups_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, tensors_dev, chunks_dev,
+                     sumsq_slots, max_norm, step_dev, groups_dev, ngroups, tensor_group_dev);
+  return check_launch("opt_adam_step_groups");
+}
+extern "C" int hrp_opt_set_group(hrp_opt_group* groups_dev, int ngroups, int index, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, void* stream) {
+  HRP_REQUIRE(groups_dev, "opt_set_group: null group table");
+  HRP_REQUIRE(ngroups >= 1, "opt_set_group: ngroups %d < 1", ngroups);
+  HRP_REQUIRE(index >= 0 && index < ngroups, "opt_set_group: index %d outside [0, %d)", index, ngroups);
+  hipLaunchKernelGGL(opt_set_group_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, groups_dev, index, lr, beta1, beta2, eps,
+                     weight_decay);
+  return check_launch("opt_set_group");
 }
 
 // ---- gradient accumulation over micro-batches: acc = (first ? 0 : acc) + scale * src over a whole gradient arena ------

@@ -5,14 +5,22 @@ The reference trains with ``torch.optim.Adam`` preceded by ``torch.nn.utils.clip
 as two table-driven launches over ALL parameters (hrp_opt_grad_sumsq, hrp_opt_adam_step in include/hrp.h):
 the multi-tensor torch path spends ~70 launches and 3 ms per step on the 57 M parameters of the full
 network, this one ~0.6 ms.  Same arithmetic as torch (fp32 state, bias correction from a device-side step
-counter so that the step is capturable into a HIP graph), no weight decay / amsgrad (the reference uses
-neither).  There is no CPU path.
+counter so that the step is capturable into a HIP graph), no amsgrad (the reference does not use it).  There is no
+CPU path.
 
 It is a ``torch.optim.Optimizer``: ``param_groups`` / ``state_dict()`` / ``load_state_dict()`` use torch.optim.Adam's
 layout (per-parameter ``step``, ``exp_avg``, ``exp_avg_sq``), so the ``optimizer_state_dict`` of the reference's
 checkpoints (lib/utils/utils.py:192-267 ``resume_run`` / ``save_checkpoint``) loads into it and what it saves loads
-into ``torch.optim.Adam``; ``LambdaLR`` (utils.py:160-189) can drive ``param_groups[0]["lr"]`` - outside a captured
-HIP graph, where the learning rate is a baked launch argument.
+into ``torch.optim.Adam``.
+
+Two paths.  Called with one list of parameters, floats and no weight decay, the step is ``hrp_opt_adam_step``: the
+hyper-parameters are launch arguments, read from ``param_groups[0]`` at every eager step and BAKED into a captured HIP
+graph.  A list of group dicts, a non-zero ``weight_decay`` or ``device_hyper=True`` selects ``hrp_opt_adam_step_groups``:
+the groups' ``lr / betas / eps / weight_decay`` live in a device table that the kernel reads when it runs, and
+``publish_hyper()`` writes the rows that changed (``hrp_opt_set_group``, on the current stream).  ``LambdaLR``
+(utils.py:147-189, ``hrpe_amd.lib.utils.utils.get_scheduler``) can drive ``param_groups[i]["lr"]`` on both paths in an eager
+loop; through a replayed graph only the second path applies the scheduled rate:
+``graph.replay(); lr_scheduler.step(); optimizer.publish_hyper()`` (get_scheduler's scheduler does the last call itself).
 """
 import ctypes as C
 
@@ -22,16 +30,27 @@ from . import _native as nv
 
 
 class FusedClipAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=None):
-        params = [p for p in params if p.requires_grad]
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_norm=None, weight_decay=0.0, device_hyper=False):
+        params = list(params)
+        grouped = any(isinstance(p, dict) for p in params)
+        if grouped:
+            if not all(isinstance(p, dict) for p in params):
+                raise ValueError("FusedClipAdam: either parameters or parameter-group dicts, not both")
+            params = [dict(g, params=[p for p in g["params"] if p.requires_grad]) for g in params]
+            params = [g for g in params if g["params"]]
+        else:
+            params = [p for p in params if p.requires_grad]
         if not params:
             raise ValueError("FusedClipAdam: no parameters")
-        if any(isinstance(p, dict) for p in params):
-            raise ValueError("FusedClipAdam: one parameter group only")
+        # the device-table path (module docstring); without it nothing differs from the one-group class: same defaults, same launches
+        self._device_hyper = bool(grouped or device_hyper or weight_decay)
         super().__init__(params, dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
-                                      weight_decay=0, amsgrad=False, maximize=False, foreach=None, capturable=True,
-                                      differentiable=False, fused=None))
-        self.params = self.param_groups[0]["params"]
+                                      weight_decay=float(weight_decay) if self._device_hyper else 0, amsgrad=False,
+                                      maximize=False, foreach=None, capturable=True, differentiable=False, fused=None))
+        for g in self.param_groups:
+            if g["amsgrad"] or g["maximize"]:
+                raise ValueError("FusedClipAdam: amsgrad / maximize are not supported")
+        self.params = [p for g in self.param_groups for p in g["params"]] if self._device_hyper else self.param_groups[0]["params"]
         dev = self.params[0].device
         if dev.type != "cuda":
             raise nv.HrpError("FusedClipAdam runs on an MI355X (gfx950) only; there is no CPU path")
@@ -55,6 +74,39 @@ class FusedClipAdam(torch.optim.Optimizer):
         self._grad_ptrs = None
         self._tensors = self._chunks = None
         self._nchunks = 0
+        if self._device_hyper:
+            ng = len(self.param_groups)
+            self._groups = torch.zeros(ng * C.sizeof(nv.OptGroup) // 4, dtype=torch.float32, device=dev)
+            self._tensor_group = torch.tensor([i for i, g in enumerate(self.param_groups) for _ in g["params"]],
+                                              dtype=torch.int32, device=dev)
+            self._hyper_mirror = [None] * ng          # what the device table holds, per group
+            self.publish_hyper()
+
+    def _hyper(self, g):
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+
+    def hyper_is_stale(self):
+        """True when some group's lr / betas / eps / weight_decay differ from what the device table was last given."""
+        return self._device_hyper and any(self._hyper(g) != m for g, m in zip(self.param_groups, self._hyper_mirror))
+
+    def publish_hyper(self):
+        """Write the groups whose ``param_groups`` values changed into the device table (one tiny launch each, on the
+        current stream, so it is ordered after a replay issued there).  Nothing to do on the launch-argument path.  Not
+        during a capture: a captured setter would rewrite the captured values at every replay."""
+        if not self._device_hyper:
+            return
+        s = None
+        for i, g in enumerate(self.param_groups):
+            h = self._hyper(g)
+            if h == self._hyper_mirror[i]:
+                continue
+            if s is None:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("FusedClipAdam.publish_hyper() during a HIP graph capture: publish before the capture "
+                                       "and after every replay")
+                s = torch.cuda.current_stream(self.device).cuda_stream
+            nv.call("hrp_opt_set_group", self._groups.data_ptr(), len(self.param_groups), i, *h, s)
+            self._hyper_mirror[i] = h
 
     def _publish_state(self):
         """torch.optim.Adam's per-parameter state, as views of the flat moment buffers and the shared step counter."""
@@ -70,11 +122,14 @@ class FusedClipAdam(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         """Accepts torch.optim.Adam's (or this class's) state_dict: moments are copied into the flat buffers."""
-        if len(state_dict["param_groups"]) != 1:
+        if not self._device_hyper and len(state_dict["param_groups"]) != 1:
             raise ValueError("FusedClipAdam: one parameter group only")
-        g = state_dict["param_groups"][0]
-        if g.get("weight_decay", 0) or g.get("amsgrad", False) or g.get("maximize", False):
-            raise ValueError("FusedClipAdam: weight_decay / amsgrad / maximize are not supported")
+        for g in state_dict["param_groups"]:
+            if self._device_hyper:
+                if g.get("amsgrad", False) or g.get("maximize", False):
+                    raise ValueError("FusedClipAdam: amsgrad / maximize are not supported")
+            elif g.get("weight_decay", 0) or g.get("amsgrad", False) or g.get("maximize", False):
+                raise ValueError("FusedClipAdam: weight_decay / amsgrad / maximize are not supported")
         super().load_state_dict(state_dict)
         steps = set()
         with torch.no_grad():
@@ -90,7 +145,8 @@ class FusedClipAdam(torch.optim.Optimizer):
             if len(steps) > 1:
                 raise ValueError(f"FusedClipAdam: parameters at different step counts {sorted(steps)}")
             self.step_count.fill_(steps.pop() if steps else 0.0)
-        self.param_groups[0]["capturable"] = True
+        for g in self.param_groups:
+            g["capturable"] = True
         self._publish_state()
 
     def _build_tables(self):
@@ -125,6 +181,12 @@ class FusedClipAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         if closure is not None:
             raise ValueError("FusedClipAdam: closures are not supported")
+        if self._device_hyper:
+            if not torch.cuda.is_current_stream_capturing():
+                self.publish_hyper()
+            elif self.hyper_is_stale():
+                raise RuntimeError("FusedClipAdam: param_groups changed since the device table was written and a HIP graph is being "
+                                   "captured; call publish_hyper() before the capture (and after every replay)")
         self.prepare()
         g = self.param_groups[0]
         s = torch.cuda.current_stream(self.device).cuda_stream
@@ -134,9 +196,14 @@ class FusedClipAdam(torch.optim.Optimizer):
             # coefficient, bit for bit, from the same averaged gradients - replicas stay identical
             nv.call("hrp_opt_grad_sumsq", self._tensors.data_ptr(), self._chunks.data_ptr(), self._nchunks,
                     self._slots.data_ptr(), self._chunk_sums.data_ptr(), s)
-        nv.call("hrp_opt_adam_step", self._tensors.data_ptr(), self._chunks.data_ptr(), self._nchunks,
-                self._slots.data_ptr(), self.max_norm, self.step_count.data_ptr(),
-                float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), s)
+        if self._device_hyper:
+            nv.call("hrp_opt_adam_step_groups", self._tensors.data_ptr(), self._chunks.data_ptr(), self._nchunks,
+                    self._slots.data_ptr(), self.max_norm, self.step_count.data_ptr(),
+                    self._groups.data_ptr(), len(self.param_groups), self._tensor_group.data_ptr(), s)
+        else:
+            nv.call("hrp_opt_adam_step", self._tensors.data_ptr(), self._chunks.data_ptr(), self._nchunks,
+                    self._slots.data_ptr(), self.max_norm, self.step_count.data_ptr(),
+                    float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), s)
         # the parameters changed through raw pointers (no tensor._version bump): inference plans must repack / refold
         from .plan import bump_param_epoch
         bump_param_epoch()

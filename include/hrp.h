@@ -435,6 +435,29 @@ int hrp_opt_grad_sumsq(const hrp_opt_tensor* tensors_dev, const hrp_opt_chunk* c
 int hrp_opt_adam_step(const hrp_opt_tensor* tensors_dev, const hrp_opt_chunk* chunks_dev, int nchunks,
                       const float* sumsq_slots, float max_norm, const float* step_dev,
                       float lr, float beta1, float beta2, float eps, void* stream);
+/* The same step with its hyper-parameters in DEVICE memory: parameter groups, torch.optim.Adam's weight_decay, and a learning
+ * rate that a scheduler changes between replays of a captured HIP graph (LambdaLR over Adam, lib/utils/utils.py:147-189;
+ * hrp_opt_adam_step bakes lr into the captured launch).  One row per parameter group: */
+typedef struct hrp_opt_group {
+  float lr, beta1, beta2, eps;
+  float weight_decay;  /* L2 as torch.optim.Adam (not AdamW): the moments see g + weight_decay * p */
+  float reserved[3];   /* 32 bytes per row */
+} hrp_opt_group;
+/* tensor_group_dev[i] = the group (row of groups_dev, in [0, ngroups)) of row i of the tensor table.  Every workgroup reads its
+ * chunk's tensor, that tensor's group and the group's five numbers when it RUNS (a few dwords per chunk, uniform over the
+ * workgroup): a replayed graph applies what the table holds at that moment.  The clip is global over all groups
+ * (clip_grad_norm_(model.parameters()): hrp_opt_grad_sumsq as above) and the clipped gradient is written back WITHOUT the decay
+ * term; with p the parameter before the update,
+ *   ge = g + weight_decay p;  m = b1 m + (1-b1) ge;  v = b2 v + (1-b2) ge^2;  p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps)
+ * A group with weight_decay == 0 runs hrp_opt_adam_step's instructions: one such group gives the same bits as that entry. */
+int hrp_opt_adam_step_groups(const hrp_opt_tensor* tensors_dev, const hrp_opt_chunk* chunks_dev, int nchunks,
+                             const float* sumsq_slots, float max_norm, const float* step_dev,
+                             const hrp_opt_group* groups_dev, int ngroups, const int32_t* tensor_group_dev, void* stream);
+/* Writes row `index` of a table of ngroups rows: a one-thread launch on `stream`, ordered like any other work there.  The values
+ * travel as launch arguments (no staging buffer that the host could overwrite while an earlier launch is queued).  NOT to be
+ * captured into the graph that holds the step: a captured setter would rewrite the captured values at every replay. */
+int hrp_opt_set_group(hrp_opt_group* groups_dev, int ngroups, int index, float lr, float beta1, float beta2, float eps,
+                      float weight_decay, void* stream);
 /* Gradient accumulation over micro-batches (PlannedModule.set_grad_accumulation): one streaming pass over a plan's flat
  * gradient arena,   acc[i] = (first ? 0 : acc[i]) + scale * src[i]   fp32, n elements, src and acc 16-byte aligned and
  * distinct.  first != 0 does not read acc (whatever it held, NaNs included, is overwritten: no memset in front).  scale == 1
