@@ -51,6 +51,7 @@ struct WgradTiling {
   int x_pieces, dy_pieces, buf_bytes;   // 1 KiB DMA pieces of the X halo tile / dY tile; one stage buffer
   int lds_tab_off, lds_red_off;
   int use_ws, lds_bytes;
+  int ring;                             // eight-wave bf16 program: stage buffers of the tile ring (2 or 3)
   // batched launch: workgroup -> (pixel share, channel-block pair) so that the workgroups which read the same 32-channel
   // slices of x / dY sit on ONE XCD (its L2 serves the re-reads).  xmode 1: >= 8 pairs - XCD k owns an xa x xb block of
   // (cout, cin) blocks for every pixel share; xmode 2: 1 / 2 / 4 pairs - XCD k owns whole pixel shares; 0: pair-major.
@@ -680,9 +681,35 @@ __global__ __launch_bounds__(256) WGRAD_OCC void conv_wgrad_kernel(const hrp_wgr
 // PAIRS = 4 on 64-pixel tiles (NKS = 2: the input halo of a 128-pixel tile does not fit): the four-wave program staged a 22 KB
 // tile per nine MFMAs of a wave there; step 34.65 -> 34.15 ms.
 // LDS: the X halo tile and the dY tile as 32-channel planes laid out exactly like the tiles of conv_wgrad_body (64-byte pixel
-// rows: the transpose reads stay conflict free), double buffered.  The partial sums leave in the 32 x 32 slab layout, so the
-// folding launches do not change.
+// rows: the transpose reads stay conflict free).  The partial sums leave in the 32 x 32 slab layout, so the folding launches do
+// not change.
+// The tile ring.  One workgroup fills a CU (144 accumulator registers per wave, 144 KB of LDS for the accumulator dump), so
+// nothing else hides its memory latency: with two stage buffers and `vmcnt(0)` at every tile only tile i + 1 is ever in flight
+// and a tile's last pieces go out a few MFMAs before the wait - one exposed round trip per tile.  PAIRS = 4 keeps THREE stage
+// buffers (40-52 KB each; they lie inside the dump's 144 KB, so the launch needs no more LDS): the prologue issues tiles gxi and
+// gxi + G, iteration i waits until only the DMAs of tile i + 1 are outstanding (`vmcnt(ndma)`: loads retire in order, ndma =
+// this wave's DMAs per tile, zero-page pieces included, so it is the same for every tile; piece p = wave + 8 slot gives waves
+// counts that differ by one, hence the wave-uniform switch over immediates in wg_wait_dma), passes the barrier - behind it every
+// wave's pieces of tile i have landed and every wave has left the buffer of tile i - 1 - and issues tile i + 2 into that
+// buffer.  Where tile i + 1 does not exist (the workgroup's last tile) the wait is vmcnt(0).  The barrier is a raw s_barrier:
+// the waits are explicit, and a fence would drain the DMAs that are meant to stay in flight.  Tile order and MFMA order per
+// tile are those of the two-buffer loop: every slab is bit-identical to what it produced.  PAIRS = 1 (512-pixel tiles of
+// 71 KB) keeps two buffers.
+//   instantiation (one kernel, wgrad_octo_batch_kernel: 230 VGPR, no AGPR, no scratch, two waves per SIMD)
+//   <4, 4>  64 x 64 block, 128-pixel tiles   stage buffer 40-52 KB x 3   launch LDS 144-156 KB
+//   <4, 2>  stride 2, 64-pixel tiles         stage buffer <= 48 KB x 3   launch LDS 144 KB
+//   <1, 4>  32 x 32 block, 512-pixel tiles   stage buffer <= 72 KB x 2   launch LDS 144 KB
 constexpr int OCTO_MAXP_X = 5, OCTO_MAXP_DY = 4;
+
+// Wait until at most `n` of this wave's DMAs are outstanding (n is wave-uniform; the count of s_waitcnt is an immediate).
+__device__ __forceinline__ void wg_wait_dma(const int n) {
+  switch (n) {
+#define HRP_VMCNT(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
+    HRP_VMCNT(1) HRP_VMCNT(2) HRP_VMCNT(3) HRP_VMCNT(4) HRP_VMCNT(5) HRP_VMCNT(6) HRP_VMCNT(7) HRP_VMCNT(8) HRP_VMCNT(9)
+#undef HRP_VMCNT
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+  }
+}
 
 template <int PAIRS, int NKS = 4>
 __device__ __forceinline__ void conv_wgrad_octo_body(const hrp_wgrad_desc& d, const WgradTiling& t, const int gxi, const int blk) {
@@ -795,12 +822,17 @@ __device__ __forceinline__ void conv_wgrad_octo_body(const hrp_wgrad_desc& d, co
   const int tr_pix = (lane & 15) >> 2;
   const int tr_coff = (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * SZ;
 
-  int it = 0;
-  if (gxi < t.ntiles) {
-    const TileCtx c = tile_ctx(gxi, smem);
+  // the tile ring: `ring` stage buffers, tiles it .. it + ring - 2 of this workgroup in flight or in use.  ndma: the DMAs this
+  // wave issues per tile (zero-page pieces included, so it is the same for every tile)
+  const int ring = (PAIRS == 1 && NKS == 4) ? 2 : t.ring, ahead = ring - 1;
+  const int ndma = __builtin_amdgcn_readfirstlane((wave < x_pieces ? (x_pieces - wave + 7) >> 3 : 0) +
+                                                  (wave < dy_pieces ? (dy_pieces - wave + 7) >> 3 : 0));
+  for (int k = 0; k < ahead; ++k)
+    if (gxi + k * t.G < t.ntiles) {
+      const TileCtx c = tile_ctx(gxi + k * t.G, smem + k * t.buf_bytes);
 #pragma unroll
-    for (int slot = 0; slot < MAXP_X + MAXP_DY; ++slot) issue_slot(c, slot);
-  }
+      for (int slot = 0; slot < MAXP_X + MAXP_DY; ++slot) issue_slot(c, slot);
+    }
   int xo0[NKS], xo1[NKS], ao[NKS];
   {
     auto xoff = [&](int m) {
@@ -817,14 +849,20 @@ __device__ __forceinline__ void conv_wgrad_octo_body(const hrp_wgrad_desc& d, co
     }
   }
 
-  for (int tile = gxi; tile < t.ntiles; tile += t.G, ++it) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const char* lds_x = smem + (it & 1) * t.buf_bytes + pci * (xpp * 1024);
-    const char* lds_dy = smem + (it & 1) * t.buf_bytes + x_pieces * 1024 + pco * (DPP * 1024);
-    const bool more = tile + t.G < t.ntiles;
+  int cur = 0, nxt = ahead;      // the stage buffers of this tile and of the tile `ahead` further on
+  for (int tile = gxi; tile < t.ntiles; tile += t.G) {
+    // This tile's pieces have landed once only the next tile's DMAs (issued after them, if it exists and the ring holds it) are
+    // outstanding.  Behind the barrier every wave's pieces are there and every wave has left buffer `nxt` (the previous tile's).
+    wg_wait_dma(ring == 3 && tile + t.G < t.ntiles ? ndma : 0);
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    const char* lds_x = smem + cur * t.buf_bytes + pci * (xpp * 1024);
+    const char* lds_dy = smem + cur * t.buf_bytes + x_pieces * 1024 + pco * (DPP * 1024);
+    const bool more = tile + ahead * t.G < t.ntiles;
     TileCtx nx{};
-    if (more) nx = tile_ctx(tile + t.G, smem + ((it + 1) & 1) * t.buf_bytes);
+    if (more) nx = tile_ctx(tile + ahead * t.G, smem + nxt * t.buf_bytes);
+    cur = cur + 1 == ring ? 0 : cur + 1;
+    nxt = nxt + 1 == ring ? 0 : nxt + 1;
     // the wave program of conv_wgrad_body (NB = 1): flattened MFMA sequence q = ks * 9 + tap, X fragments D steps ahead, the dY
     // fragment of the next k-step at the first tap; one DMA piece of the next tile every fourth (second) step
     constexpr int D = 4, TOT = NKS * NT, STRIDE = TOT / (MAXP_X + MAXP_DY);
@@ -1289,7 +1327,9 @@ static int wgrad_tiling_octo(const hrp_wgrad_desc& d, WgradTiling& t, int pairs_
   t.buf_bytes = (t.x_pieces + t.dy_pieces) * 1024;
   t.lds_tab_off = 0; t.lds_red_off = 0;
   const int red_bytes = 8 * d.ntaps * 512 * 4;
-  t.lds_bytes = 2 * t.buf_bytes > red_bytes ? 2 * t.buf_bytes : red_bytes;
+  // bf16: three stage buffers where they fit (64 x 64 blocks: at most 52 KB each next to the 144 KB of the accumulator dump)
+  t.ring = (!x3 && pairs_w == 4 && 3 * t.buf_bytes <= 160 * 1024) ? 3 : 2;
+  t.lds_bytes = t.ring * t.buf_bytes > red_bytes ? t.ring * t.buf_bytes : red_bytes;
   if (t.lds_bytes > 160 * 1024) return HRP_ERR_ARG;
   t.tiles_x = cdiv(d.Wo, TW); t.tiles_y = cdiv(d.Ho, TH); t.tiles_n = cdiv(d.N, TI);
   t.ntiles = t.tiles_x * t.tiles_y * t.tiles_n;
