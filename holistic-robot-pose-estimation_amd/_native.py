@@ -253,7 +253,26 @@ class DreamSample(C.Structure):
                 ("noise_off", C.c_int64), ("scratch_off", C.c_int64)]
 
 
-_P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
+JPEG_ERR_DATA, JPEG_ERR_MARKER, JPEG_ERR_CODE, JPEG_ERR_INDEX, JPEG_ERR_DESC, JPEG_WARN_TRAILING, JPEG_ERR_CHECKSUM = 1, 2, 4, 8, 16, 32, 64   # HRP_JPEG_*
+
+
+class JpegHuff(C.Structure):      # hrp_jpeg_huff
+    _fields_ = [("counts", C.c_uint8 * 16), ("values", C.c_uint8 * 256)]
+
+
+class JpegImage(C.Structure):     # hrp_jpeg_image
+    _fields_ = [("scan_off", C.c_int64), ("scan_len", C.c_int64), ("coef_off", C.c_int64), ("plane_off", C.c_int64),
+                ("frame_off", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("hsamp", C.c_int32), ("vsamp", C.c_int32),
+                ("restart_interval", C.c_int32), ("scan_sum", C.c_uint32), ("sum_len", C.c_int64),
+                ("comp_tq", C.c_uint8 * 4), ("comp_td", C.c_uint8 * 4), ("comp_ta", C.c_uint8 * 4), ("reserved2", C.c_uint8 * 4),
+                ("quant", (C.c_uint16 * 64) * 4), ("dc", JpegHuff * 2), ("ac", JpegHuff * 2)]
+
+
+class JpegSegment(C.Structure):   # hrp_jpeg_segment
+    _fields_ = [("off", C.c_int64), ("len", C.c_int64), ("image", C.c_int32), ("mcu0", C.c_int32)]
+
+
+_P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
 # name -> argtypes (every function returns int unless noted); mirrors include/hrp.h one to one
 PROTOTYPES = {
     "hrp_version": [], "hrp_device_ok": [],
@@ -338,6 +357,8 @@ PROTOTYPES = {
     "hrp_dream_crop_resize": [_P, _L, _P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
     "hrp_eval_batch": [C.POINTER(EvalDesc), _P],
     "hrp_depth_loss": [C.POINTER(DepthLossDesc), _P],
+    "hrp_jpeg_decode": [_P, _I, _P, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
+    "hrp_jpeg_decode_stage": [_I, _I, _P, _I, _P, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
 }
 
 _lib = None

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from hrpe_amd import _native as nv
+from hrpe_amd.lib.dataset import jpeg
 from hrpe_amd.lib.dataset.augmentations import occlusion_aug
 from hrpe_amd.lib.dataset.const import KEYPOINT_NAMES
 from hrpe_amd.lib.dataset.roboutils import bbox_transform, get_bbox, get_bbox_raw, get_extended_bbox
@@ -146,17 +147,44 @@ def _view(shared, resize_hw, extend_ratio):
             "keypoints_3d": torch.FloatTensor(kp3d), "keypoints_2d": kp2d_r, "valid_mask_crop": valid}
 
 
+class _Encoded:
+    """A frame that is not decoded in the worker (device_decode): the file's bytes and its parsed header, or - for a file that
+    jpeg.parse_header refuses - Pillow's decode as raw bytes.  ``shape`` is all that __getitem__ reads of a frame."""
+
+    def __init__(self, data):
+        from PIL import Image
+        hdr = jpeg.parse_header(data)
+        if hdr is None:
+            import io
+            host = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+            rec = np.zeros(1, dtype=jpeg.HDR_DTYPE)
+            rec["height"], rec["width"] = host.shape[0], host.shape[1]
+            self.jpeg, self.hdr, self.host = b"", rec.view(np.uint8).reshape(jpeg.HDR_BYTES), host.tobytes()
+            self.shape = host.shape
+        else:
+            r = jpeg.record(hdr)
+            self.jpeg, self.hdr, self.host = data, hdr, b""
+            self.shape = (int(r["height"]), int(r["width"]), 3)
+
+
 class DreamDataset(torch.utils.data.Dataset):
     """The reference's DreamDataset (dream.py:48-412) with the same constructor and batch schema.  __getitem__ returns, besides
     the reference's non-image entries, ``frame`` (the decoded uint8 [H, W, 3]), ``aug`` (float64 [len(AUG_FIELDS)]: the drawn
     factors and the crop geometry) and ``noise`` (bytes: the occlusion fill); ``to_device`` turns a collated batch into the
-    reference's dict on the GPU."""
+    reference's dict on the GPU.
+
+    device_decode=True leaves the JPEG decode to the GPU (lib/dataset/jpeg.py): the worker only reads the file and parses its
+    header, and the item carries ``jpeg`` (the file's bytes), ``jpeg_hdr`` (uint8 [jpeg.HDR_BYTES]) and ``jpeg_host`` in place
+    of ``frame``.  A file the device path does not take (progressive, grayscale, ...) is decoded with Pillow in the worker:
+    its ``jpeg`` is empty and ``jpeg_host`` holds the raw RGB bytes, which ``to_device`` uploads into the same frame buffer."""
 
     def __init__(self, base_dir, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), visibility_check=True,
                  strict_crop=True, color_jitter=True, rgb_augmentation=True, occlusion_augmentation=True, flip=False,
-                 rotate=False, padding=False, occlu_p=0.5, process_truncation=False, extend_ratio=[0.2, 0.13]):
+                 rotate=False, padding=False, occlu_p=0.5, process_truncation=False, extend_ratio=[0.2, 0.13],
+                 device_decode=False):
         if flip or rotate or padding:
             raise NotImplementedError("DreamDataset: flip / rotate / padding are not implemented (no shipped config enables them)")
+        self.device_decode = device_decode
         self.base_dir = Path(base_dir)
         self.ds_name = os.path.basename(base_dir)
         self.rootnet_resize_hw, self.other_resize_hw = rootnet_resize_hw, other_resize_hw
@@ -190,7 +218,7 @@ class DreamDataset(torch.utils.data.Dataset):
         from PIL import Image
         row = self.frame_index.iloc[idx]
         rgb_path = Path(row.rgb_path)
-        rgb = np.asarray(Image.open(rgb_path))
+        rgb = _Encoded(rgb_path.read_bytes()) if self.device_decode else np.asarray(Image.open(rgb_path))
         ann = json.loads(rgb_path.with_suffix("").with_suffix(".json").read_text())
         h, w = rgb.shape[0], rgb.shape[1]
         cam_path = self.base_dir / "_camera_settings.json"
@@ -292,10 +320,14 @@ class DreamDataset(torch.utils.data.Dataset):
         for k, v in (("pad_x", pad_x), ("pad_y", pad_y), ("work_w", work_w), ("work_h", work_h), ("crop_x0", x0),
                      ("crop_y0", y0), ("crop_x1", x1), ("crop_y1", y1), ("off_x", off_x), ("off_y", off_y), ("side", side)):
             aug[_A[k]] = v
+        if isinstance(rgb, _Encoded):
+            frame = {"jpeg": rgb.jpeg, "jpeg_hdr": torch.from_numpy(rgb.hdr.copy()), "jpeg_host": rgb.host}
+        else:
+            frame = {"frame": torch.from_numpy(np.array(rgb, dtype=np.uint8))}
         return {
             "image_id": idx,
             "scene_id": row.scene_id,
-            "frame": torch.from_numpy(np.array(rgb, dtype=np.uint8)),
+            **frame,
             "aug": torch.from_numpy(aug),
             "noise": noise,
             "bbox_strict_bounded_original": shared["bbox_strict_bounded_original"],
@@ -310,13 +342,15 @@ class DreamDataset(torch.utils.data.Dataset):
             "other": _view(shared, self.other_resize_hw, self.extend_ratio),
         }
 
-    def to_device(self, batch, device=None, stream=None):
+    def to_device(self, batch, device=None, stream=None, jpeg_status=None):
         """A collated batch -> the reference's batch dict on `device` (default: the current CUDA device), with the pixel work of
         the whole batch in two launches on the current stream.  ``images_original`` is the decoded frame as uint8 [B, 3, H, W]
         (a view of the uploaded [B, H, W, 3]); ``root/images`` and ``other/images`` are uint8 [B, 3, h, w].  When the two
         views have the same size (every shipped config: 256 x 256) they are written once and both entries hold the same
-        tensor."""
-        return to_device(batch, self.rootnet_resize_hw, self.other_resize_hw, device=device, stream=stream)
+        tensor.  A batch of a device_decode dataset is decoded on the GPU first; by default the decode's status is checked
+        before returning (which synchronises) - pass a list as jpeg_status to receive the status tensor instead and call
+        jpeg.check_status on it later."""
+        return to_device(batch, self.rootnet_resize_hw, self.other_resize_hw, device=device, stream=stream, jpeg_status=jpeg_status)
 
 
 def _move(v, device):
@@ -384,12 +418,46 @@ def pixel_launches(frames, table, noise, scratch, lsum, out0, out1=None, max_hw=
             out0.data_ptr(), out0.shape[2], out0.shape[3], out1.data_ptr() if out1 is not None else None, h1, w1, s)
 
 
-def to_device(batch, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), device=None, stream=None):
+def decode_frames(datas, hdrs, hosts, device, stream=None):
+    """The frames of a device_decode batch as one uint8 [B, H, W, 3] device tensor, and the decode's status ([B] int32 on the
+    device, None when no file went to the GPU): the files with a header in one jpeg.Batch, the frames that the worker decoded
+    (``hosts``, raw RGB bytes) uploaded into the same buffer.  All frames of a batch have one size, as ``frame`` requires."""
+    recs = jpeg.record(hdrs)
+    B = len(datas)
+    if recs.shape != (B,) or len(hosts) != B:
+        raise nv.HrpError(f"DreamDataset batch: {B} jpeg entries, {recs.shape} headers, {len(hosts)} host frames")
+    H, W = int(recs["height"][0]), int(recs["width"][0])
+    if H < 1 or W < 1 or (recs["height"] != H).any() or (recs["width"] != W).any():
+        raise nv.HrpError("DreamDataset batch: the frames of a batch must have one size")
+    on_dev = [i for i in range(B) if len(datas[i])]
+    for i in range(B):
+        if (len(datas[i]) == 0) == (len(hosts[i]) == 0) or len(hosts[i]) not in (0, H * W * 3):
+            raise nv.HrpError(f"DreamDataset batch: sample {i} needs either its file or its {H} x {W} decoded frame")
+    if len(on_dev) == B:
+        b = jpeg.Batch(datas, recs, device)
+        b.launch(stream)
+        return b.flat.view(B, H, W, 3), b.status
+    frames_d = torch.empty(B, H, W, 3, dtype=torch.uint8, device=device)
+    status = None
+    if on_dev:
+        b = jpeg.Batch([datas[i] for i in on_dev], recs[on_dev], device)
+        b.launch(stream)
+        frames_d[torch.as_tensor(on_dev, device=device)] = b.flat.view(len(on_dev), H, W, 3)
+        status = b.status
+    host = [i for i in range(B) if len(hosts[i])]
+    up = torch.from_numpy(np.frombuffer(b"".join(hosts[i] for i in host), dtype=np.uint8).copy()).to(device, non_blocking=True)
+    frames_d[torch.as_tensor(host, device=device)] = up.view(len(host), H, W, 3)
+    return frames_d, status
+
+
+def to_device(batch, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), device=None, stream=None, jpeg_status=None):
     """DreamDataset.to_device for a collated batch (see there)."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if device.type != "cuda":
         raise nv.HrpError(f"DreamDataset.to_device: {device} is not a GPU (there is no CPU path for the pixel work)")
     nv.lib()
+    if "jpeg" in batch:
+        return _to_device_jpeg(batch, rootnet_resize_hw, other_resize_hw, device, stream, jpeg_status)
     frames = torch.as_tensor(batch["frame"])
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise nv.HrpError(f"DreamDataset.to_device: frames {tuple(frames.shape)} {frames.dtype}, want uint8 [B, H, W, 3]")
@@ -397,6 +465,27 @@ def to_device(batch, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), d
     tab, noise, scratch_bytes = descriptor_table(batch["aug"], batch["noise"])
     mh, mw = int(max(H, tab["work_h"].max())), int(max(W, tab["work_w"].max()))
     frames_d = frames.to(device, non_blocking=True).contiguous()
+    return _pixel_work(batch, frames_d, tab, noise, scratch_bytes, (mh, mw), rootnet_resize_hw, other_resize_hw, device, stream)
+
+
+def _to_device_jpeg(batch, rootnet_resize_hw, other_resize_hw, device, stream, jpeg_status):
+    """to_device for a batch that carries ``jpeg`` / ``jpeg_hdr`` / ``jpeg_host`` in place of ``frame``."""
+    tab, noise, scratch_bytes = descriptor_table(batch["aug"], batch["noise"])
+    frames_d, status = decode_frames(batch["jpeg"], batch["jpeg_hdr"], batch["jpeg_host"], device, stream)
+    _, H, W, _ = frames_d.shape
+    mh, mw = int(max(H, tab["work_h"].max())), int(max(W, tab["work_w"].max()))
+    out = _pixel_work(batch, frames_d, tab, noise, scratch_bytes, (mh, mw), rootnet_resize_hw, other_resize_hw, device, stream)
+    if jpeg_status is not None:
+        jpeg_status.append(status)
+    elif status is not None:
+        jpeg.check_status(status)
+    return out
+
+
+def _pixel_work(batch, frames_d, tab, noise, scratch_bytes, max_hw, rootnet_resize_hw, other_resize_hw, device, stream):
+    """The part of to_device after the frames are on the device: the two launches and the batch dict."""
+    B = frames_d.shape[0]
+    mh, mw = max_hw
     table_d = torch.from_numpy(tab.view(np.uint8).copy()).to(device, non_blocking=True)
     noise_d = torch.from_numpy(np.frombuffer(noise, dtype=np.uint8).copy()).to(device, non_blocking=True)
     scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=device)
@@ -407,7 +496,8 @@ def to_device(batch, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), d
     same = (hr, wr) == (ho, wo)
     out_o = out_r if same else torch.empty(B, 3, ho, wo, dtype=torch.uint8, device=device)
     pixel_launches(frames_d, table_d, noise_d, scratch, lsum, out_r, None if same else out_o, max_hw=(mh, mw), stream=stream)
-    out = {k: _move(v, device) for k, v in batch.items() if k not in ("frame", "aug", "noise", "root", "other")}
+    out = {k: _move(v, device) for k, v in batch.items()
+           if k not in ("frame", "jpeg", "jpeg_hdr", "jpeg_host", "aug", "noise", "root", "other")}
     out["images_original"] = frames_d.permute(0, 3, 1, 2)
     out["root"] = dict(_move(batch["root"], device), images=out_r)
     out["other"] = dict(_move(batch["other"], device), images=out_o)

@@ -58,10 +58,14 @@
  *                             xy branch, multi_kp), its gradient, and the per-image errors of the validation pass into
  *                             epoch-length device accumulators
  *                                                     scripts/train_depthnet.py:220-268, 276-303
+ *   hrp_jpeg_decode           the JPEG decode behind DreamDataset's np.asarray(Image.open(rgb_path)) for baseline files: entropy
+ *                             decoding, inverse DCT, chroma up-sampling and colour conversion of a batch
+ *                                                     lib/dataset/dream.py:110
  */
 #ifndef HRP_H
 #define HRP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -949,6 +953,65 @@ typedef struct hrp_depth_loss_desc {
   int32_t batch_index, batch_capacity;
 } hrp_depth_loss_desc;
 int hrp_depth_loss(const hrp_depth_loss_desc* d, void* stream);
+
+/* Baseline JPEG decode of a batch on the device (csrc/jpeg.hip; the decoder itself is csrc/jpeg_core.h, the same functions for the
+ * kernels and for a host compiler).  The host (lib/dataset/jpeg.py) parses each file's header into one hrp_jpeg_image and splits
+ * its scan at the restart markers into hrp_jpeg_segment records; the device does entropy decoding, dequantisation, libjpeg's
+ * "islow" inverse DCT, "fancy" chroma up-sampling and the YCbCr -> RGB step, byte-exact with libjpeg-turbo's defaults (Pillow).
+ * Supported: SOF0, 8 bit, three components in one interleaved scan, luma sampling 1x1 / 2x1 / 2x2 with 1x1 chroma, down-sampled
+ * chroma wider than 2 columns.  One call may mix sizes and sub-samplings.
+ *   bytes    the files' bytes (at least every scan), one upload; a segment is bytes[off, off + len) and holds no marker
+ *   coef     int16, 16-byte aligned: image i owns 64 * blocks(i) values at coef_off, quantised, natural order, the blocks of
+ *            component 0 in raster order, then those of component 1, then 2; blocks(i) counts whole MCUs
+ *   planes   uint8: the component planes of image i (padded to whole MCUs, 64 * blocks(i) bytes) at plane_off, same order
+ *   frames   uint8: the [height, width, 3] RGB frame of image i at frame_off
+ *   status   int32 [B]: 0, or the HRP_JPEG_ERR_* bits of what stopped a segment of the image (its remaining coefficients are zero)
+ *            and HRP_JPEG_WARN_TRAILING
+ * Five launches (clear, checksum, entropy, inverse DCT, colour) whatever the images hold, caller-owned buffers, no host synchronisation:
+ * graph-capturable.  The kernels check every offset of every descriptor against nbytes / ncoef / nplanes / nframes and leave an
+ * image whose descriptor does not fit untouched, with HRP_JPEG_ERR_DESC. */
+enum {
+  HRP_JPEG_ERR_DATA = 1,    /* the segment ran out of data */
+  HRP_JPEG_ERR_MARKER = 2,  /* a marker inside the segment */
+  HRP_JPEG_ERR_CODE = 4,    /* no Huffman code of 16 bits or fewer matches */
+  HRP_JPEG_ERR_INDEX = 8,   /* a run leads past coefficient 63 */
+  HRP_JPEG_ERR_DESC = 16,   /* the descriptor, a table or a segment record is inconsistent */
+  HRP_JPEG_ERR_CHECKSUM = 64,   /* bytes[scan_off, scan_off + sum_len) are not the bytes the header was parsed from: their Adler-32
+                                   is not scan_sum.  It ties a descriptor to its bytes on their separate ways from the loader worker
+                                   to the device; damage that a file took before it was parsed is outside its reach */
+  HRP_JPEG_WARN_TRAILING = 32   /* every MCU decoded, but the segment goes on: whole bytes are left, or padding bits that are not
+                                   ones (a decoder that lost step with the encoder usually ends here) */
+};
+typedef struct hrp_jpeg_huff {
+  uint8_t counts[16];       /* number of codes of length 1..16 (DHT's BITS) */
+  uint8_t values[256];      /* the symbols in code order (DHT's HUFFVAL) */
+} hrp_jpeg_huff;
+typedef struct hrp_jpeg_image {
+  int64_t scan_off, scan_len;       /* the entropy-coded bytes of the scan within `bytes`; every segment lies inside */
+  int64_t coef_off;                 /* first int16 of the image in coef (a multiple of 64) */
+  int64_t plane_off, frame_off;     /* first byte of the image in planes / frames */
+  int32_t width, height;
+  int32_t hsamp, vsamp;             /* luma sampling factors: 1x1, 2x1 or 2x2 (chroma is 1x1) */
+  int32_t restart_interval;         /* MCUs per segment (DRI); 0: the whole scan is one segment */
+  uint32_t scan_sum;                /* Adler-32 (zlib's) of bytes[scan_off, scan_off + sum_len), taken when the header was parsed */
+  int64_t sum_len;                  /* from the first entropy-coded byte to the end of the file: sum_len >= scan_len */
+  uint8_t comp_tq[4], comp_td[4], comp_ta[4];   /* per component: quantisation, DC and AC table selectors (entry 3 unused) */
+  uint8_t reserved2[4];
+  uint16_t quant[4][64];            /* quantisation tables, natural (row-major) order */
+  hrp_jpeg_huff dc[2], ac[2];
+} hrp_jpeg_image;
+typedef struct hrp_jpeg_segment {
+  int64_t off, len;                 /* bytes[off, off + len): one restart interval, or the whole scan */
+  int32_t image, mcu0;              /* the image it belongs to and its first MCU (raster order) */
+} hrp_jpeg_segment;
+int hrp_jpeg_decode(const hrp_jpeg_image* images_dev, int B, const hrp_jpeg_segment* segments_dev, int nseg, const uint8_t* bytes,
+                    size_t nbytes, int16_t* coef, size_t ncoef, uint8_t* planes, size_t nplanes, uint8_t* frames, size_t nframes,
+                    int32_t* status, void* stream);
+/* The stages on their own, for tools/bench_jpeg.py: stage 0 the clear + checksum + entropy launches, 1 the inverse DCT + colour launches.
+ * lanes: segments per 64-lane wave of the entropy kernel, 1..64 (0: the default). */
+int hrp_jpeg_decode_stage(int stage, int lanes, const hrp_jpeg_image* images_dev, int B, const hrp_jpeg_segment* segments_dev,
+                          int nseg, const uint8_t* bytes, size_t nbytes, int16_t* coef, size_t ncoef, uint8_t* planes, size_t nplanes,
+                          uint8_t* frames, size_t nframes, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
