@@ -359,6 +359,9 @@ PROTOTYPES = {
     "hrp_depth_loss": [C.POINTER(DepthLossDesc), _P],
     "hrp_jpeg_decode": [_P, _I, _P, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
     "hrp_jpeg_decode_stage": [_I, _I, _P, _I, _P, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
+    "hrp_jpeg_decode_sync": [_P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
+    "hrp_jpeg_decode_sync_stage": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
+    "hrp_jpeg_sync_scratch_bytes": [_Z, _I, _I],      # returns size_t (set in lib())
 }
 
 _lib = None
@@ -413,6 +416,7 @@ def lib():
         L.hrp_batch_table_bytes.argtypes = [C.c_int, C.c_int]
         L.hrp_block_table_bytes.restype = C.c_int64
         L.hrp_block_table_bytes.argtypes = []
+        L.hrp_jpeg_sync_scratch_bytes.restype = C.c_size_t
         _lib = L
     return _lib
 

@@ -403,4 +403,269 @@ JPEG_HD void jpeg_pixel(const hrp_jpeg_image& d, const Geom& g, const uint8_t* p
   rgb[2] = clamp_u8(yy + ((116130 * cb + 32768) >> 16));
 }
 
+// ---- one segment decoded by many lanes (hrp_jpeg_decode_sync) --------------------------------------------------------------------
+// The segment is cut into sub-sequences of S raw bytes; sub-sequence i owns every symbol (a Huffman code and its magnitude
+// bits) that BEGINS in it, the last one everything to the end of the segment.  The state between two symbols is one word:
+//   bits 16..  the raw bit position within the segment, 8 * byte + bit, the byte never the 00 of a stuffed FF 00; with bit 0
+//              it names the next data byte (after an FF, the byte behind its 00), and at the end of the stream the byte where
+//              the reader stops.  Two lanes that started at different places and fell into step give the same number.
+//   bits 8..15 unit: the block's index inside the MCU, 0 .. hsamp * vsamp + 1
+//   bits 0..7  k: the zig-zag index of the next coefficient, 0: a DC code comes next
+// jpeg_sync_subseq decodes one sub-sequence from an entry state.  Without `fin` it writes nothing and its results are a pure
+// function of the entry state and the bytes; what ends a segment in jpeg_decode_segment is met by a fixed rule instead
+// (SyncSums::hit counts those events):
+//   a code that does not exist,
+//   a DC category above 15          16 bits are skipped and the block is abandoned: unit + 1, k = 0, not counted
+//   a run past coefficient 63       the block is abandoned
+//   a bit past the end of the data  the exit state is the end of the segment (bit 8 * len, unit 0, k 0), on which every later
+//                                   sub-sequence decodes nothing
+// Up to the first such event the chain of exit states from the true start (bit 0, unit 0, k 0) is the serial decoder's; the
+// sub-sequences behind the first one with a hit are dead in the final pass.  With `fin` the entry state is the true one,
+// blk0 the number of blocks the segment completed before it and pred0[] the DC predictors there (the sums of the DC
+// differences so far, modulo 2^16): it writes what jpeg_decode_segment writes, stops where that stops and returns its bits.
+typedef uint64_t SyncState;
+constexpr SyncState SYNC_DEAD = ~(SyncState)0;
+constexpr int SYNC_SERIAL = 1 << 30;      // fin: whether the status has HRP_JPEG_ERR_MARKER is for jpeg_segment_status to say
+
+struct SyncSums {      // of the symbols that begin in one sub-sequence; after the prefix sum, of all sub-sequences before it
+  uint32_t blocks;     // blocks completed
+  uint16_t dc[3];      // sum of the DC differences per component, modulo 2^16
+  uint16_t hit;        // events of the list above
+};
+
+JPEG_HD SyncState sync_state(uint64_t bit, int unit, int k) { return (bit << 16) | ((uint64_t)(unit & 255) << 8) | (uint64_t)(k & 255); }
+
+// the first bit of sub-sequence i > 0 with a guessed unit and k: where every lane but the first starts
+JPEG_HD SyncState sync_guess(const hrp_jpeg_image& d, const uint8_t* seg, int64_t lo, int unit, int k) {
+  const int nu = d.hsamp * d.vsamp + 2;
+  if (seg[lo - 1] == 0xFF && seg[lo] == 0) ++lo;      // the 00 of a stuffed pair is not data
+  return sync_state((uint64_t)lo * 8, unit < 0 ? 0 : (unit < nu ? unit : nu - 1), k < 0 ? 0 : (k < 63 ? k : 63));
+}
+
+// the raw bit position of the next unread bit.  The reader has loaded up to b.p; of its look-ahead, every FF took two raw bytes.
+JPEG_HD uint64_t sync_pos(const Bits& b, const uint8_t* seg) {
+  const int real = b.n - b.fake, m = (real + 7) >> 3;
+  int ff = 0;
+  if (m) {
+    uint64_t w = b.acc >> b.fake;
+    if (m < 8) w &= (1ull << (8 * m)) - 1;
+    w &= w >> 1;
+    w &= w >> 2;
+    w &= w >> 4;
+    ff = __builtin_popcountll(w & 0x0101010101010101ull);
+  }
+  return (uint64_t)((b.p - seg) - m - ff) * 8 + (uint64_t)((8 - (real & 7)) & 7);
+}
+
+// the last MCU of a segment and the number of its blocks
+JPEG_HD uint32_t sync_segment_blocks(const hrp_jpeg_image& d, const Geom& g, const hrp_jpeg_segment& s) {
+  const int total = g.mcux * g.mcuy;
+  const int last = d.restart_interval ? (s.mcu0 + d.restart_interval < total ? s.mcu0 + d.restart_interval : total) : total;
+  return (uint32_t)(last - s.mcu0) * (uint32_t)(d.hsamp * d.vsamp + 2);
+}
+
+// block `blk` of the segment in scan order, `unit` inside its MCU: its index among the image's blocks
+JPEG_HD size_t sync_block(const hrp_jpeg_image& d, const Geom& g, const hrp_jpeg_segment& s, uint32_t blk, int unit) {
+  const int nl = d.hsamp * d.vsamp, c = unit < nl ? 0 : unit - nl + 1;
+  const int m = s.mcu0 + (int)(blk / (uint32_t)(nl + 2)), my = m / g.mcux, mx = m - my * g.mcux;
+  const int v = c ? 0 : unit / d.hsamp, h = c ? 0 : unit - v * d.hsamp;
+  return (size_t)g.base[c] + (size_t)(my * (c ? 1 : d.vsamp) + v) * g.bw[c] + mx * (c ? 1 : d.hsamp) + h;
+}
+
+// hi: the end of the sub-sequence within the segment, INT64_MAX for the last one
+JPEG_HD int jpeg_sync_subseq(const hrp_jpeg_image& d, const Geom& g, const hrp_jpeg_segment& s, const uint8_t* bytes, const Tables& t,
+                             int64_t hi, SyncState entry, SyncState& exit_out, SyncSums& sums_out, bool fin, uint32_t blk0, const uint16_t* pred0,
+                             int16_t* coef) {
+  SyncState exit = entry;      // results in registers; stored once, where the function returns
+  SyncSums sums = {0, {0, 0, 0}, 0};
+  auto finish = [&](int err) {
+    exit_out = exit;
+    sums_out = sums;
+    return err;
+  };
+  const int nl = d.hsamp * d.vsamp, nu = nl + 2;
+  int unit = (int)((entry >> 8) & 255), k = (int)(entry & 255);
+  const uint64_t bit0 = entry >> 16;
+  if (entry == SYNC_DEAD || unit >= nu || k > 63 || bit0 > (uint64_t)s.len * 8) {
+    exit = SYNC_DEAD;
+    return finish(0);
+  }
+  const int64_t e = (int64_t)(bit0 >> 3);
+  if (e >= hi) return finish(0);      // the symbol before ran past this sub-sequence, or the stream has ended
+  const uint32_t nblk = sync_segment_blocks(d, g, s);
+  uint32_t blk = blk0;
+  if (fin && blk >= nblk) return finish(0);      // behind the last MCU
+  int16_t* out = fin ? coef + sync_block(d, g, s, blk, unit) * 64 : coef;
+  const uint8_t* seg = bytes + s.off;
+  Bits b;
+  bits_open(b, seg + e, (size_t)(s.len - e));
+  bool ended = false;      // a bit was taken that the stream does not have, at a place where jpeg_decode_block looks
+  if (bit0 & 7) {
+    bits_fill(b);
+    bits_skip(b, (int)(bit0 & 7));
+    ended = b.err != 0;
+  }
+  while (!ended) {
+    if (b.n <= 32) bits_fill(b);      // a symbol is 32 bits at the most: no fill inside one
+    const uint64_t pos = sync_pos(b, seg);
+    if ((int64_t)(pos >> 3) >= hi) {
+      exit = sync_state(pos, unit, k);
+      return finish(0);
+    }
+    const int c = unit < nl ? 0 : unit - nl + 1;
+    bool done = false, drop = false;      // the block is complete / abandoned
+    if (k == 0) {
+      const int sz = huff_decode(b, t.lut[d.comp_td[c]]);
+      if (sz < 0) {
+        drop = true;
+      } else if (sz > 15) {
+        b.err |= HRP_JPEG_ERR_CODE;
+        drop = true;
+      } else {
+        const int diff = sz ? huff_extend(bits_get(b, sz), sz) : 0;
+        if (b.err) {
+          ended = true;
+        } else {
+          const uint16_t sum = (uint16_t)((c == 0 ? sums.dc[0] : (c == 1 ? sums.dc[1] : sums.dc[2])) + diff);      // no indexed register array
+          sums.dc[0] = c == 0 ? sum : sums.dc[0];
+          sums.dc[1] = c == 1 ? sum : sums.dc[1];
+          sums.dc[2] = c == 2 ? sum : sums.dc[2];
+          k = 1;
+          if (fin) out[0] = (int16_t)(uint16_t)(pred0[c] + sum);      // the predictor: every difference of the component so far
+        }
+      }
+    } else {
+      const int rs = huff_decode(b, t.lut[2 + d.comp_ta[c]]);
+      if (rs < 0) {
+        drop = true;
+      } else if ((rs & 15) == 0) {
+        if ((rs >> 4) != 15) {      // end of block
+          done = b.err == 0;
+          ended = !done;
+        } else {                    // sixteen zeros; a coefficient has to follow
+          k += 16;
+          if (k > 63) {
+            b.err |= HRP_JPEG_ERR_INDEX;
+            drop = true;
+          }
+        }
+      } else {
+        k += rs >> 4;
+        if (k > 63) {
+          b.err |= HRP_JPEG_ERR_INDEX;
+          drop = true;
+        } else {
+          const int v = huff_extend(bits_get(b, rs & 15), rs & 15);
+          if (b.err) {
+            ended = true;
+          } else {
+            if (fin) out[t.natural[k]] = (int16_t)v;
+            done = ++k == 64;
+          }
+        }
+      }
+    }
+    if (ended) break;
+    if (drop) {
+      ++sums.hit;
+      if (fin) return finish(b.err);
+      if (b.err & HRP_JPEG_ERR_CODE) bits_skip(b, 16);                     // set by huff_decode or for the category: both skip
+      if (b.err & (HRP_JPEG_ERR_DATA | HRP_JPEG_ERR_MARKER)) break;      // that took a bit the stream does not have: it has ended
+      b.err = 0;
+    }
+    if (done || drop) {
+      k = 0;
+      unit = unit + 1 == nu ? 0 : unit + 1;
+    }
+    if (done) {
+      ++sums.blocks;
+      if (++blk == nblk && fin) {
+        // Behind the last MCU: what jpeg_decode_segment checks there.  With R bits of the stream left, R < 8: its reader has
+        // met the end, so has this one, and both see the same bits.  R >= 8: the warning is certain; whether that reader had
+        // met a marker by then depends on how far ahead it had loaded, which only its own history says.
+        if (b.n <= 32) bits_fill(b);
+        const int real = b.n - b.fake;
+        if (real < 8) {
+          int err = b.stop == HRP_JPEG_ERR_MARKER ? HRP_JPEG_ERR_MARKER : 0;
+          if (real > 0 && ((uint32_t)(b.acc >> b.fake) & ((1u << real) - 1u)) != (1u << real) - 1u) err |= HRP_JPEG_WARN_TRAILING;
+          return finish(err);
+        }
+        const uint8_t* q = b.p;
+        int stop = b.stop;
+        for (int r = real; !stop && r <= 64; r += 8) {
+          if (q >= b.end || (*q == 0xFF && b.end - q < 2)) stop = HRP_JPEG_ERR_DATA;
+          else if (*q != 0xFF) ++q;
+          else if (q[1] == 0) q += 2;
+          else stop = HRP_JPEG_ERR_MARKER;
+        }
+        return finish(HRP_JPEG_WARN_TRAILING | (stop == HRP_JPEG_ERR_MARKER ? SYNC_SERIAL : 0));
+      }
+      if (fin) out = coef + sync_block(d, g, s, blk, unit) * 64;
+    }
+  }
+  ++sums.hit;
+  exit = sync_state((uint64_t)s.len * 8, 0, 0);
+  return finish(fin ? b.err : 0);
+}
+
+// The status that jpeg_decode_segment returns, without its writes: `block` is 64 values of the caller's to decode into.
+// For the one case above that the position alone does not settle.
+JPEG_HD int jpeg_segment_status(const hrp_jpeg_image& d, const Geom& g, const hrp_jpeg_segment& s, const uint8_t* bytes, const Tables& t,
+                                int16_t* block) {
+  Bits b;
+  bits_open(b, bytes + s.off, (size_t)s.len);
+  const uint32_t nblk = sync_segment_blocks(d, g, s);
+  const int nl = d.hsamp * d.vsamp, nu = nl + 2;
+  int pred[3] = {0, 0, 0};
+  for (uint32_t blk = 0; blk < nblk; ++blk) {
+    const int unit = (int)(blk % (uint32_t)nu), c = unit < nl ? 0 : unit - nl + 1;
+    if (!jpeg_decode_block(b, t.lut[d.comp_td[c]], t.lut[2 + d.comp_ta[c]], t.natural, pred[c], block)) return b.err;
+  }
+  if (b.n <= 32) bits_fill(b);
+  const int real = b.n - b.fake;
+  if (b.stop == HRP_JPEG_ERR_MARKER) b.err |= HRP_JPEG_ERR_MARKER;
+  if (!b.stop || real >= 8 || (real > 0 && ((uint32_t)(b.acc >> b.fake) & ((1u << real) - 1u)) != (1u << real) - 1u)) b.err |= HRP_JPEG_WARN_TRAILING;
+  return b.err;
+}
+
+// What the lanes of one segment share, 32 bytes per sub-sequence in the caller's scratch.  The segment with index j in the list
+// of long segments owns the slots from sync_region(off, j, S) on: one SyncHead, then one SyncSlot per sub-sequence.  Segments in
+// ascending order that do not overlap get regions that do not overlap, inside sync_slots(nbytes, nlong, S) slots.
+struct SyncSlot {
+  SyncState entry, exit;
+  SyncSums sums;
+  uint32_t redo;       // the entry changed in this round
+};
+struct SyncHead {
+  uint32_t rounds;     // rounds of step (b), the one in which nothing changed included
+  uint32_t subseqs;
+  uint32_t wrong;      // sub-sequences whose first, speculative exit state was not the final one
+  uint32_t pad[5];
+};
+static_assert(sizeof(SyncSlot) == 32 && sizeof(SyncHead) == 32, "one slot is 32 bytes");
+
+JPEG_HD uint64_t sync_slots(uint64_t nbytes, uint64_t nlong, uint64_t S) { return nbytes / S + 2 * nlong + 1; }
+JPEG_HD uint64_t sync_region(uint64_t off, uint64_t j, uint64_t S) { return off / S + 2 * j; }
+JPEG_HD int64_t sync_hi(int64_t i, int64_t n, int64_t S) { return i + 1 >= n ? INT64_MAX : (i + 1) * S; }
+
+// step (a): sub-sequence i from the true start (i = 0) or from the guess
+JPEG_HD void jpeg_sync_first(const hrp_jpeg_image& d, const Geom& g, const hrp_jpeg_segment& s, const uint8_t* bytes, const Tables& t,
+                             int64_t i, int64_t n, int64_t S, int guess_unit, int guess_k, SyncSlot& sl) {
+  sl.entry = i ? sync_guess(d, bytes + s.off, i * S, guess_unit, guess_k) : sync_state(0, 0, 0);
+  sl.redo = 0;
+  jpeg_sync_subseq(d, g, s, bytes, t, sync_hi(i, n, S), sl.entry, sl.exit, sl.sums, false, 0, nullptr, nullptr);
+}
+
+// step (c), after the prefix sum has turned sl.sums into those of everything before sub-sequence i.  The HRP_JPEG_* bits; with
+// SYNC_SERIAL set when they took jpeg_segment_status (`block`: 64 values to decode into).
+JPEG_HD int jpeg_sync_final(const hrp_jpeg_image& d, const Geom& g, const hrp_jpeg_segment& s, const uint8_t* bytes, const Tables& t,
+                            int64_t i, int64_t n, int64_t S, const SyncSlot& sl, int16_t* coef, int16_t* block) {
+  if (sl.sums.hit) return 0;      // the segment ended before this sub-sequence
+  SyncState x;
+  SyncSums u;
+  int err = jpeg_sync_subseq(d, g, s, bytes, t, sync_hi(i, n, S), sl.entry, x, u, true, sl.sums.blocks, sl.sums.dc, coef);
+  if (err & SYNC_SERIAL) err |= jpeg_segment_status(d, g, s, bytes, t, block) & HRP_JPEG_ERR_MARKER;
+  return err;
+}
+
 }  // namespace jpeg

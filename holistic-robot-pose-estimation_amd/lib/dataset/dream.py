@@ -176,15 +176,19 @@ class DreamDataset(torch.utils.data.Dataset):
     device_decode=True leaves the JPEG decode to the GPU (lib/dataset/jpeg.py): the worker only reads the file and parses its
     header, and the item carries ``jpeg`` (the file's bytes), ``jpeg_hdr`` (uint8 [jpeg.HDR_BYTES]) and ``jpeg_host`` in place
     of ``frame``.  A file the device path does not take (progressive, grayscale, ...) is decoded with Pillow in the worker:
-    its ``jpeg`` is empty and ``jpeg_host`` holds the raw RGB bytes, which ``to_device`` uploads into the same frame buffer."""
+    its ``jpeg`` is empty and ``jpeg_host`` holds the raw RGB bytes, which ``to_device`` uploads into the same frame buffer.
+    jpeg_entropy="sync" makes ``to_device`` decode with jpeg.Batch(entropy="sync"): a file without restart markers by a whole
+    workgroup instead of one lane, with the same result."""
 
     def __init__(self, base_dir, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), visibility_check=True,
                  strict_crop=True, color_jitter=True, rgb_augmentation=True, occlusion_augmentation=True, flip=False,
                  rotate=False, padding=False, occlu_p=0.5, process_truncation=False, extend_ratio=[0.2, 0.13],
-                 device_decode=False):
+                 device_decode=False, jpeg_entropy="segment"):
         if flip or rotate or padding:
             raise NotImplementedError("DreamDataset: flip / rotate / padding are not implemented (no shipped config enables them)")
-        self.device_decode = device_decode
+        if jpeg_entropy not in ("segment", "sync"):
+            raise nv.HrpError(f"DreamDataset: jpeg_entropy {jpeg_entropy!r}, want 'segment' or 'sync'")
+        self.device_decode, self.jpeg_entropy = device_decode, jpeg_entropy
         self.base_dir = Path(base_dir)
         self.ds_name = os.path.basename(base_dir)
         self.rootnet_resize_hw, self.other_resize_hw = rootnet_resize_hw, other_resize_hw
@@ -342,15 +346,17 @@ class DreamDataset(torch.utils.data.Dataset):
             "other": _view(shared, self.other_resize_hw, self.extend_ratio),
         }
 
-    def to_device(self, batch, device=None, stream=None, jpeg_status=None):
+    def to_device(self, batch, device=None, stream=None, jpeg_status=None, jpeg_entropy=None, subseq_bytes=None, min_subseq=None):
         """A collated batch -> the reference's batch dict on `device` (default: the current CUDA device), with the pixel work of
         the whole batch in two launches on the current stream.  ``images_original`` is the decoded frame as uint8 [B, 3, H, W]
         (a view of the uploaded [B, H, W, 3]); ``root/images`` and ``other/images`` are uint8 [B, 3, h, w].  When the two
         views have the same size (every shipped config: 256 x 256) they are written once and both entries hold the same
         tensor.  A batch of a device_decode dataset is decoded on the GPU first; by default the decode's status is checked
         before returning (which synchronises) - pass a list as jpeg_status to receive the status tensor instead and call
-        jpeg.check_status on it later."""
-        return to_device(batch, self.rootnet_resize_hw, self.other_resize_hw, device=device, stream=stream, jpeg_status=jpeg_status)
+        jpeg.check_status on it later.  jpeg_entropy (default: the constructor's), subseq_bytes and min_subseq go to jpeg.Batch."""
+        return to_device(batch, self.rootnet_resize_hw, self.other_resize_hw, device=device, stream=stream, jpeg_status=jpeg_status,
+                         jpeg_entropy=self.jpeg_entropy if jpeg_entropy is None else jpeg_entropy, subseq_bytes=subseq_bytes,
+                         min_subseq=min_subseq)
 
 
 def _move(v, device):
@@ -418,10 +424,12 @@ def pixel_launches(frames, table, noise, scratch, lsum, out0, out1=None, max_hw=
             out0.data_ptr(), out0.shape[2], out0.shape[3], out1.data_ptr() if out1 is not None else None, h1, w1, s)
 
 
-def decode_frames(datas, hdrs, hosts, device, stream=None):
+def decode_frames(datas, hdrs, hosts, device, stream=None, entropy="segment", subseq_bytes=None, min_subseq=None):
     """The frames of a device_decode batch as one uint8 [B, H, W, 3] device tensor, and the decode's status ([B] int32 on the
     device, None when no file went to the GPU): the files with a header in one jpeg.Batch, the frames that the worker decoded
-    (``hosts``, raw RGB bytes) uploaded into the same buffer.  All frames of a batch have one size, as ``frame`` requires."""
+    (``hosts``, raw RGB bytes) uploaded into the same buffer.  All frames of a batch have one size, as ``frame`` requires.
+    entropy, subseq_bytes, min_subseq: jpeg.Batch's."""
+    kw = dict(entropy=entropy, subseq_bytes=subseq_bytes, min_subseq=min_subseq)
     recs = jpeg.record(hdrs)
     B = len(datas)
     if recs.shape != (B,) or len(hosts) != B:
@@ -434,13 +442,13 @@ def decode_frames(datas, hdrs, hosts, device, stream=None):
         if (len(datas[i]) == 0) == (len(hosts[i]) == 0) or len(hosts[i]) not in (0, H * W * 3):
             raise nv.HrpError(f"DreamDataset batch: sample {i} needs either its file or its {H} x {W} decoded frame")
     if len(on_dev) == B:
-        b = jpeg.Batch(datas, recs, device)
+        b = jpeg.Batch(datas, recs, device, **kw)
         b.launch(stream)
         return b.flat.view(B, H, W, 3), b.status
     frames_d = torch.empty(B, H, W, 3, dtype=torch.uint8, device=device)
     status = None
     if on_dev:
-        b = jpeg.Batch([datas[i] for i in on_dev], recs[on_dev], device)
+        b = jpeg.Batch([datas[i] for i in on_dev], recs[on_dev], device, **kw)
         b.launch(stream)
         frames_d[torch.as_tensor(on_dev, device=device)] = b.flat.view(len(on_dev), H, W, 3)
         status = b.status
@@ -450,14 +458,16 @@ def decode_frames(datas, hdrs, hosts, device, stream=None):
     return frames_d, status
 
 
-def to_device(batch, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), device=None, stream=None, jpeg_status=None):
+def to_device(batch, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), device=None, stream=None, jpeg_status=None,
+              jpeg_entropy="segment", subseq_bytes=None, min_subseq=None):
     """DreamDataset.to_device for a collated batch (see there)."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if device.type != "cuda":
         raise nv.HrpError(f"DreamDataset.to_device: {device} is not a GPU (there is no CPU path for the pixel work)")
     nv.lib()
     if "jpeg" in batch:
-        return _to_device_jpeg(batch, rootnet_resize_hw, other_resize_hw, device, stream, jpeg_status)
+        return _to_device_jpeg(batch, rootnet_resize_hw, other_resize_hw, device, stream, jpeg_status,
+                               dict(entropy=jpeg_entropy, subseq_bytes=subseq_bytes, min_subseq=min_subseq))
     frames = torch.as_tensor(batch["frame"])
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
         raise nv.HrpError(f"DreamDataset.to_device: frames {tuple(frames.shape)} {frames.dtype}, want uint8 [B, H, W, 3]")
@@ -468,10 +478,10 @@ def to_device(batch, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256), d
     return _pixel_work(batch, frames_d, tab, noise, scratch_bytes, (mh, mw), rootnet_resize_hw, other_resize_hw, device, stream)
 
 
-def _to_device_jpeg(batch, rootnet_resize_hw, other_resize_hw, device, stream, jpeg_status):
+def _to_device_jpeg(batch, rootnet_resize_hw, other_resize_hw, device, stream, jpeg_status, jpeg_kw):
     """to_device for a batch that carries ``jpeg`` / ``jpeg_hdr`` / ``jpeg_host`` in place of ``frame``."""
     tab, noise, scratch_bytes = descriptor_table(batch["aug"], batch["noise"])
-    frames_d, status = decode_frames(batch["jpeg"], batch["jpeg_hdr"], batch["jpeg_host"], device, stream)
+    frames_d, status = decode_frames(batch["jpeg"], batch["jpeg_hdr"], batch["jpeg_host"], device, stream, **jpeg_kw)
     _, H, W, _ = frames_d.shape
     mh, mw = int(max(H, tab["work_h"].max())), int(max(W, tab["work_w"].max()))
     out = _pixel_work(batch, frames_d, tab, noise, scratch_bytes, (mh, mw), rootnet_resize_hw, other_resize_hw, device, stream)

@@ -6,6 +6,10 @@ components, sampling other than 4:4:4 / 4:2:2 / 4:2:0, several scans, an Adobe m
 down-sampled chroma plane of two columns or fewer.  ``decode_batch`` uploads the files' bytes in one copy, splits every scan at
 its restart markers, fills in the offsets and launches the decode; the frames equal Pillow's (libjpeg-turbo defaults) byte for
 byte.  ``status`` stays on the device: ``check_status`` is the call that synchronises and raises.  There is no CPU path.
+
+``entropy="sync"`` (``Batch``, ``decode_batch``; default ``"segment"``) selects hrp_jpeg_decode_sync: segments of at least
+``min_subseq`` sub-sequences of ``subseq_bytes`` bytes - a file without restart markers is one such segment - are decoded by one
+workgroup each from speculative start points, the others by the one-lane kernel as before.  Same frames, coefficients and status.
 """
 import zlib
 
@@ -17,6 +21,11 @@ from hrpe_amd import _native as nv
 HDR_DTYPE = np.dtype(nv.JpegImage)
 SEG_DTYPE = np.dtype(nv.JpegSegment)
 HDR_BYTES = HDR_DTYPE.itemsize
+# entropy="sync": the sub-sequence size (the fastest of 32 / 64 / 128 / 256 on 127 KB scans), and how many sub-sequences make a
+# segment a long one (the smallest value that keeps 4.2 KB restart intervals on the one-lane kernel, where they are faster).
+# DESIGN 7.7 has the measurements.
+SUBSEQ_BYTES = 256
+MIN_SUBSEQ = 18
 ERR_MASK = nv.JPEG_ERR_DATA | nv.JPEG_ERR_MARKER | nv.JPEG_ERR_CODE | nv.JPEG_ERR_INDEX | nv.JPEG_ERR_DESC | nv.JPEG_ERR_CHECKSUM
 
 # zig-zag position -> natural (row-major) index
@@ -181,11 +190,29 @@ def split_segments(buf, recs):
     return np.concatenate(segs)
 
 
+def split_long(segs, subseq_bytes, min_subseq):
+    """(short, long): the segments that span fewer than min_subseq sub-sequences of subseq_bytes bytes, and the others; both in
+    the order of `segs` (ascending offsets, as hrp_jpeg_decode_sync wants its long list)."""
+    is_long = -(-segs["len"].astype(np.int64) // int(subseq_bytes)) >= int(min_subseq)
+    is_long &= segs["len"] > 0
+    return segs[~is_long], segs[is_long]
+
+
 class Batch:
     """The buffers of one decode on the device, and the arguments of hrp_jpeg_decode for them (a fixed set of caller-owned
-    buffers: ``launch`` can be captured in a graph and replayed)."""
+    buffers: ``launch`` can be captured in a graph and replayed).  entropy="sync": of hrp_jpeg_decode_sync, with ``scratch``
+    among the buffers and the segments in two lists, ``short`` and ``long``."""
 
-    def __init__(self, datas, records, device):
+    def __init__(self, datas, records, device, entropy="segment", subseq_bytes=None, min_subseq=None):
+        if entropy not in ("segment", "sync"):
+            raise nv.HrpError(f"jpeg Batch: entropy {entropy!r}, want 'segment' or 'sync'")
+        S = SUBSEQ_BYTES if subseq_bytes is None else int(subseq_bytes)
+        m = MIN_SUBSEQ if min_subseq is None else int(min_subseq)
+        if entropy == "sync" and (S < 16 or S > 4096 or S & (S - 1) or m < 1):
+            raise nv.HrpError(f"jpeg Batch: sub-sequences of {S} bytes (want a power of two in 16 .. 4096), min_subseq {m} (want >= 1)")
+        if entropy == "sync" and torch.device(device).type != "cuda":
+            raise nv.HrpError(f"jpeg Batch: {device} is not a GPU (there is no CPU path)")
+        self.entropy, self.subseq_bytes, self.min_subseq = entropy, S, m
         recs = np.array(record(records), dtype=HDR_DTYPE, ndmin=1).copy()
         B = len(datas)
         if B < 1 or recs.shape != (B,):
@@ -209,6 +236,10 @@ class Batch:
         self.shapes = [(int(r["height"]), int(r["width"])) for r in recs]
         up = lambda a: torch.from_numpy(a.view(np.uint8).copy()).to(device, non_blocking=True)   # noqa: E731
         self.images_d, self.segments_d, self.bytes_d = up(recs), up(segs), up(buf)
+        if entropy == "sync":
+            self.short, self.long = split_long(segs, S, m)
+            self.short_d, self.long_d = (up(a) if len(a) else None for a in (self.short, self.long))
+            self.scratch = torch.empty(32 * (len(buf) // S + 2 * len(self.long) + 1), dtype=torch.uint8, device=device)
         ncoef = int(blocks.sum()) * 64
         self.coef = torch.empty(ncoef, dtype=torch.int16, device=device)
         self.planes = torch.empty(ncoef, dtype=torch.uint8, device=device)
@@ -221,8 +252,26 @@ class Batch:
                 self.bytes_d.numel(), self.coef.data_ptr(), self.coef.numel(), self.planes.data_ptr(), self.planes.numel(),
                 self.flat.data_ptr(), self.flat.numel(), self.status.data_ptr(), s)
 
+    def sync_args(self, stream=None):
+        """The arguments of hrp_jpeg_decode_sync (entropy="sync")."""
+        a = self.args(stream)
+        ptr = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        return (a[0], a[1], ptr(self.short_d), len(self.short), ptr(self.long_d), len(self.long), self.subseq_bytes) + a[4:12] + \
+            (self.scratch.data_ptr(), self.scratch.numel()) + a[12:]
+
     def launch(self, stream=None):
-        nv.call("hrp_jpeg_decode", *self.args(stream))
+        if self.entropy == "sync":
+            nv.call("hrp_jpeg_decode_sync", *self.sync_args(stream))
+        else:
+            nv.call("hrp_jpeg_decode", *self.args(stream))
+
+    def rounds(self):
+        """entropy="sync", after a launch (synchronises): the rounds each long segment's workgroup needed, the last one - in
+        which nothing changed - included."""
+        if not len(self.long):
+            return np.zeros(0, dtype=np.uint32)
+        slot = self.long["off"].astype(np.int64) // self.subseq_bytes + 2 * np.arange(len(self.long))
+        return self.scratch.view(torch.int32)[torch.as_tensor(slot * 8, device=self.scratch.device)].cpu().numpy().astype(np.uint32)
 
     def frames(self):
         """One [H, W, 3] uint8 view of the frame buffer per image."""
@@ -230,10 +279,11 @@ class Batch:
         return [self.flat[int(o):int(o) + h * w * 3].view(h, w, 3) for o, (h, w) in zip(offs, self.shapes)]
 
 
-def decode_batch(datas, records, device, stream=None):
+def decode_batch(datas, records, device, stream=None, entropy="segment", subseq_bytes=None, min_subseq=None):
     """datas: list of the files' bytes; records: their parse_header results (a list, or the collated [B, HDR_BYTES] array /
-    tensor).  One upload, one hrp_jpeg_decode call on `stream` (default: the current stream).  Returns (frames, status): a
-    list of uint8 [H, W, 3] device tensors (views of one buffer) and the int32 [B] status on the device."""
+    tensor).  One upload, one hrp_jpeg_decode call on `stream` (default: the current stream); entropy="sync": one
+    hrp_jpeg_decode_sync call (see Batch).  Returns (frames, status): a list of uint8 [H, W, 3] device tensors (views of one
+    buffer) and the int32 [B] status on the device."""
     device = torch.device(device)
     if device.type != "cuda":
         raise nv.HrpError(f"jpeg decode_batch: {device} is not a GPU (there is no CPU path)")
@@ -242,7 +292,7 @@ def decode_batch(datas, records, device, stream=None):
         if any(r is None for r in records):
             raise nv.HrpError("jpeg decode_batch: a file without a header record (parse_header refused it: decode it on the host)")
         records = np.stack([np.asarray(r, dtype=np.uint8) for r in records])
-    b = Batch(datas, records, device)
+    b = Batch(datas, records, device, entropy=entropy, subseq_bytes=subseq_bytes, min_subseq=min_subseq)
     b.launch(stream)
     return b.frames(), b.status
 

@@ -61,6 +61,8 @@
  *   hrp_jpeg_decode           the JPEG decode behind DreamDataset's np.asarray(Image.open(rgb_path)) for baseline files: entropy
  *                             decoding, inverse DCT, chroma up-sampling and colour conversion of a batch
  *                                                     lib/dataset/dream.py:110
+ *   hrp_jpeg_decode_sync      the same with a long segment (a file without restart markers) decoded by one workgroup from
+ *                             speculative start points
  */
 #ifndef HRP_H
 #define HRP_H
@@ -1012,6 +1014,37 @@ int hrp_jpeg_decode(const hrp_jpeg_image* images_dev, int B, const hrp_jpeg_segm
 int hrp_jpeg_decode_stage(int stage, int lanes, const hrp_jpeg_image* images_dev, int B, const hrp_jpeg_segment* segments_dev,
                           int nseg, const uint8_t* bytes, size_t nbytes, int16_t* coef, size_t ncoef, uint8_t* planes, size_t nplanes,
                           uint8_t* frames, size_t nframes, int32_t* status, void* stream);
+
+/* The same decode with a second entropy stage for long segments (files without restart markers are one segment each).  A long
+ * segment is cut into sub-sequences of subseq_bytes raw bytes (a power of two, 16 .. 4096) and decoded by one workgroup: every
+ * lane decodes a sub-sequence from a guessed state (Huffman-coded scans fall into step after a few dozen symbols), the lanes pass
+ * their exit states on in rounds until none changes - at that point every state is exact, so the number of rounds is not capped -
+ * prefix sums give every sub-sequence its block number and its DC predictors, and a final pass writes the coefficients.  coef,
+ * planes, frames and status end up exactly as hrp_jpeg_decode leaves them, for damaged scans too (csrc/jpeg_core.h,
+ * tests/jpeg_sync_host_check.cpp).
+ *   short_segments_dev [nshort]  go through hrp_jpeg_decode's one-lane kernel
+ *   long_segments_dev [nlong]    one workgroup each; in ascending order of `off`, not overlapping, len > 0
+ *                                either count may be 0, not both
+ *   scratch  16-byte aligned, at least hrp_jpeg_sync_scratch_bytes(nbytes, nlong, subseq_bytes) =
+ *            32 * (nbytes / subseq_bytes + 2 * nlong + 1) bytes (0 for a subseq_bytes that is not taken).  Every call rewrites what
+ *            it reads there.  Long segment j owns the 32-byte slots from off / subseq_bytes + 2 * j on: first {uint32 rounds,
+ *            uint32 sub-sequences, uint32 sub-sequences whose exit state changed after the first pass}, then one slot per
+ *            sub-sequence.
+ * Clear, checksum, one launch per non-empty segment list, inverse DCT, colour: a launch count fixed by the arguments, caller-owned
+ * buffers, no host synchronisation, no workgroup waits for another: graph-capturable.  The kernels check every descriptor and
+ * the scratch size as hrp_jpeg_decode's do. */
+size_t hrp_jpeg_sync_scratch_bytes(size_t nbytes, int nlong, int subseq_bytes);
+int hrp_jpeg_decode_sync(const hrp_jpeg_image* images_dev, int B, const hrp_jpeg_segment* short_segments_dev, int nshort,
+                         const hrp_jpeg_segment* long_segments_dev, int nlong, int subseq_bytes, const uint8_t* bytes, size_t nbytes,
+                         int16_t* coef, size_t ncoef, uint8_t* planes, size_t nplanes, uint8_t* frames, size_t nframes, void* scratch,
+                         size_t nscratch, int32_t* status, void* stream);
+/* Its stages on their own, for tools/bench_jpeg.py and the tests: stage 0 the entropy launches, 1 the pixel launches.  guess_unit,
+ * guess_k: the state every sub-sequence but the first starts from (block within the MCU, zig-zag index; hrp_jpeg_decode_sync
+ * passes 0, 0; the result does not depend on them, the number of rounds does). */
+int hrp_jpeg_decode_sync_stage(int stage, int guess_unit, int guess_k, const hrp_jpeg_image* images_dev, int B,
+                               const hrp_jpeg_segment* short_segments_dev, int nshort, const hrp_jpeg_segment* long_segments_dev, int nlong,
+                               int subseq_bytes, const uint8_t* bytes, size_t nbytes, int16_t* coef, size_t ncoef, uint8_t* planes,
+                               size_t nplanes, uint8_t* frames, size_t nframes, void* scratch, size_t nscratch, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

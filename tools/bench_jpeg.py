@@ -7,6 +7,10 @@ Device events after warm-up, five rounds, median and spread (min .. max) of:
     image) and with one restart interval per MCU row (30 segments per image),
   * the pixel stage (inverse DCT + colour launches),
   * the whole hrp_jpeg_decode call,
+  * the same with the many-lanes-per-segment entropy stage (jpeg.Batch(entropy="sync")): its entropy stage and the whole
+    hrp_jpeg_decode_sync call at 32, 64, 128 and 256 bytes per sub-sequence with every segment a long one, the rounds the batch
+    needed (the maximum over its segments), and the call at jpeg.SUBSEQ_BYTES for several values of min_subseq and for the
+    default one,
   * the upload of the compressed bytes against the upload of the decoded frames (pageable host memory, as to_device has it),
 and, on the host, Pillow's single-thread decode per frame.  Every decode is checked against Pillow's bytes before it is timed.
 ``python tools/bench_jpeg.py [--out FILE.json]``"""
@@ -80,6 +84,24 @@ def main():
             r[f"entropy_lanes{lanes}"] = rounds(lambda: nv.call("hrp_jpeg_decode_stage", 0, lanes, *a), 1, 3)
         r["pixel"] = rounds(lambda: nv.call("hrp_jpeg_decode_stage", 1, 0, *a), 3, 20)
         r["decode"] = rounds(b.launch, 1, 3)
+        hdrs = np.stack([J.parse_header(d) for d in datas])
+
+        def sync(S, m):
+            bs = J.Batch(datas, hdrs, DEV, entropy="sync", subseq_bytes=S, min_subseq=m)
+            bs.launch()
+            J.check_status(bs.status)
+            assert torch.equal(bs.flat, b.flat) and torch.equal(bs.coef, b.coef), "the sync decode differs from the segment path"
+            sa = bs.sync_args()
+            out = {"long": len(bs.long), "short": len(bs.short), "rounds_max": int(bs.rounds().max()) if len(bs.long) else 0,
+                   "entropy": rounds(lambda: nv.call("hrp_jpeg_decode_sync_stage", 0, 0, 0, *sa), 2, 5),
+                   "decode": rounds(bs.launch, 2, 5)}
+            return out
+        for S in (32, 64, 128, 256):
+            r[f"sync_subseq{S}"] = sync(S, 1)
+        for m in (4, 16, 17, 18, 32):
+            r[f"sync_min_subseq{m}"] = sync(J.SUBSEQ_BYTES, m)
+        r["sync_defaults"] = dict(sync(J.SUBSEQ_BYTES, J.MIN_SUBSEQ), subseq_bytes=J.SUBSEQ_BYTES, min_subseq=J.MIN_SUBSEQ)
+        r["decode_again"] = rounds(b.launch, 1, 3)      # the segment path once more, behind the sync rows
         res[label] = r
         if not kw:
             comp = torch.from_numpy(np.frombuffer(b"".join(datas), dtype=np.uint8).copy())
