@@ -175,6 +175,19 @@ class DepthLossDesc(C.Structure):
                                          "batch_capacity")]
 
 
+SIM2REAL_ROW = ("loss", "loss_joint", "loss_rot", "loss_trans", "loss_uv", "loss_depth", "loss_error2d", "loss_error3d", "loss_mask",
+                "loss_scale", "loss_iou", "loss_error3d_align")       # the order of hrp_sim2real_monitor's row
+
+
+class Sim2RealMonitorDesc(C.Structure):
+    """hrp_sim2real_monitor_desc (include/hrp.h): predictions, ground truth, mask terms, outputs, sizes."""
+    INPUTS = ("pose", "rot", "trans", "root_uv", "depth", "xyz_fk", "gt_pose", "gt_root_rot", "gt_root_trans", "gt_root_uv",
+              "gt_kp3d", "gt_kp2d", "mask", "K")
+    _fields_ = [(n, C.c_void_p) for n in INPUTS + ("mask_terms", "row", "meters", "rows")] + \
+               [("B", C.c_int32), ("P", C.c_int32), ("J", C.c_int32), ("image_size", C.c_float), ("row_index", C.c_int32),
+                ("capacity", C.c_int32)]
+
+
 OPT_CHUNK = 4096
 
 
@@ -357,6 +370,7 @@ PROTOTYPES = {
     "hrp_dream_crop_resize": [_P, _L, _P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
     "hrp_eval_batch": [C.POINTER(EvalDesc), _P],
     "hrp_depth_loss": [C.POINTER(DepthLossDesc), _P],
+    "hrp_sim2real_monitor": [C.POINTER(Sim2RealMonitorDesc), _P],
     "hrp_jpeg_decode": [_P, _I, _P, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
     "hrp_jpeg_decode_stage": [_I, _I, _P, _I, _P, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
     "hrp_jpeg_decode_sync": [_P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],

@@ -58,6 +58,10 @@
  *                             xy branch, multi_kp), its gradient, and the per-image errors of the validation pass into
  *                             epoch-length device accumulators
  *                                                     scripts/train_depthnet.py:220-268, 276-303
+ *   hrp_sim2real_monitor      the self-supervised trainer's per-step bookkeeping: the seven supervised terms it logs, next to the
+ *                             mask terms of hrp_sim2real_loss, into meters that live on the device
+ *                                                     scripts/train_sim2real.py:313-400, 558-569, 649-660;
+ *                                                     lib/utils/transforms.py:17-21
  *   hrp_jpeg_decode           the JPEG decode behind DreamDataset's np.asarray(Image.open(rgb_path)) for baseline files: entropy
  *                             decoding, inverse DCT, chroma up-sampling and colour conversion of a batch
  *                                                     lib/dataset/dream.py:110
@@ -955,6 +959,41 @@ typedef struct hrp_depth_loss_desc {
   int32_t batch_index, batch_capacity;
 } hrp_depth_loss_desc;
 int hrp_depth_loss(const hrp_depth_loss_desc* d, void* stream);
+
+/* The bookkeeping of one step of the self-supervised trainer in ONE launch (csrc/sim2real_step.hip): the seven supervised terms
+ * scripts/train_sim2real.py:313-400 computes for its logs - detached there (:396-398), so there is no gradient - and the twelve
+ * values the training loop and validate hand to their AverageValueMeters (:649-660, :558-569).  All tensors dense fp32.
+ * S = image_size, gt_root_depth = gt_root_trans[:, 2] (:208).
+ *   loss_joint    mean (pose - gt_pose)^2                                                                    (:321-322)
+ *   loss_rot      mean (rot - gt_root_rot)^2                                                                 (:330-331)
+ *   loss_depth    mean |depth - gt_root_depth|                                                               (:337-338)
+ *   loss_uv       mean_b ||(root_uv - gt_root_uv) / S||_2 - UNMASKED, unlike lib/core/function.py:231-235    (:350-353)
+ *   loss_trans    e_b = ||trans - gt_root_trans||_2, m = mean e; m > 0.5: mean(e exp(-20 e)), else m         (:363-370)
+ *   loss_error3d  mean over (b, k) of ||xyz_fk - gt_kp3d||_2                                                 (:374-377)
+ *   loss_error2d  sum ||proj(K, xyz_fk) / S - gt_kp2d / S||_2 mask / sum (mask != 0), proj = (K p)[:2] / (K p)[2]
+ *                 (lib/utils/transforms.py:17-21); an all-zero mask gives 0 / 0 = NaN as torch does           (:243, 381-386)
+ * row[12] = loss, loss_joint, loss_rot, loss_trans, loss_uv, loss_depth, loss_error2d, loss_error3d, loss_mask, loss_scale,
+ * loss_iou, loss_error3d_align.  row[0] = mask_terms[0] and row[8..11] = mask_terms[1], [3], [2], [4], mask_terms being the five
+ * floats hrp_sim2real_loss wrote (loss, mask, iou, scale, align); mask_terms NULL (validation): those five are zero (:399-402).
+ * meters (optional, 8-byte aligned): double sum[12] followed by int64 count; the launch adds row (widened to double, slots in
+ * index order) to sum and 1 to count - a host-side memset resets them, nothing has to reach the host per step.  rows (optional)
+ * [capacity, 12]: row is also written at row_index.  One workgroup; every sum runs over k within a sample, then over the samples,
+ * in index order (no atomics): bit-reproducible.  B <= 0, a null required pointer, J > HRP_FK_MAX_KP, P > HRP_FK_MAX_JOINTS or
+ * row_index >= capacity: HRP_ERR_ARG, nothing launches. */
+typedef struct hrp_sim2real_monitor_desc {
+  const float *pose, *rot, *trans, *root_uv, *depth, *xyz_fk;            /* [B,P] [B,6] [B,3] [B,2] [B,1] [B,J,3]       (:240-241) */
+  const float *gt_pose, *gt_root_rot, *gt_root_trans, *gt_root_uv;      /* [B,P] [B,6] [B,3] [B,2]                     (:188-209) */
+  const float *gt_kp3d, *gt_kp2d, *mask;                                /* [B,J,3] [B,J,2] [B,J] of the "other" crop   (:165-167) */
+  const float* K;                                                       /* [B,9] other_K                                   (:155) */
+  const float* mask_terms;                                              /* [5] of hrp_sim2real_loss, or NULL                      */
+  float* row;                                                           /* [12]                                                   */
+  void* meters;                                                         /* optional: double sum[12], int64 count                  */
+  float* rows;                                                          /* optional [capacity, 12]                                */
+  int32_t B, P, J;              /* J <= HRP_FK_MAX_KP, P <= HRP_FK_MAX_JOINTS */
+  float image_size;
+  int32_t row_index, capacity;
+} hrp_sim2real_monitor_desc;
+int hrp_sim2real_monitor(const hrp_sim2real_monitor_desc* d, void* stream);
 
 /* Baseline JPEG decode of a batch on the device (csrc/jpeg.hip; the decoder itself is csrc/jpeg_core.h, the same functions for the
  * kernels and for a host compiler).  The host (lib/dataset/jpeg.py) parses each file's header into one hrp_jpeg_image and splits

@@ -2,7 +2,10 @@
 """The self-supervised (render-and-compare) training step of BASELINE config 5 on synthetic data, timed on one GPU (development /
 evidence tool - bench.py's contract is the supervised step).  Reference loop body: scripts/train_sim2real.py:139-146, 405-418, 435-468.
 
-    python tools/bench_sim2real.py [--batch 32] [--steps 10] [--faces-per-side 14]
+    python tools/bench_sim2real.py [--batch 32] [--steps 10] [--faces-per-side 14] [--library-step]
+
+--library-step drives the same step through the library (lib/core/sim2real.py: farward_loss on a DREAM-shaped batch with a TrainMeters,
+one read every tenth step as at scripts/train_sim2real.py:662) instead of the hand-composed sequence below.
 
 What is synthetic: the images, the robot mesh (one box per visual-mesh link, every side a grid of triangles: ~21 000 faces at the
 default, the size of a real visual mesh set) and the weights of both networks.  The mask network (seg_mask_inference: device-side
@@ -61,8 +64,75 @@ def main():
     ap.add_argument("--faces-per-side", type=int, default=14)
     ap.add_argument("--mask-target", choices=["rendered", "net"], default="rendered")
     ap.add_argument("--no-mask-net", action="store_true")
+    ap.add_argument("--library-step", action="store_true")
     a = ap.parse_args()
     print(json.dumps(run(a)))
+
+
+class _OffsetTrans(torch.nn.Module):
+    """The model with the constant per-sample offset of run() added to its predicted translation."""
+
+    def __init__(self, model, t_off):
+        super().__init__()
+        self.model, self.t_off = model, t_off
+
+    def forward(self, reg_images, root_images, k_values, K=None):
+        out = tuple(self.model(reg_images, root_images, k_values, K))
+        return out[:2] + (out[2] + self.t_off,) + out[3:]
+
+
+def library_step(a, model, d, K_original, renderer, t_off, seg, seg_net, images_original_255, weights, opt):
+    """The step of run() through lib/core/sim2real.py: a DREAM-shaped batch (uint8 crops, as DreamDataset.to_device hands them over)
+    goes through farward_loss - prepare_batch, the model, seg_net, the rendered masks, sim2real_mask_loss and ONE monitor launch
+    that advances a TrainMeters - then backward and clip + Adam.  The meters are read every tenth step (train_sim2real.py:662)."""
+    import types
+    from hrpe_amd.lib.core import sim2real as S
+    from hrpe_amd.lib.dataset.const import JOINT_NAMES
+    from hrpe_amd.lib.utils.geometries import rotmat_to_rot6d
+    from hrpe_amd.lib.utils.transforms import point_projection_from_3d_tensor
+    B = a.batch
+    robot = model.robot
+    kp3d = robot.get_keypoints(d["q"], rotmat_to_rot6d(d["R"]), d["t"])
+    TCO = torch.eye(4, device=DEV).repeat(B, 1, 1)
+    TCO[:, :3, :3], TCO[:, :3, 3] = d["R"], d["t"]
+    u8 = lambda x: (x * 255.0).to(torch.uint8)   # noqa: E731
+    view = {"K": d["K"], "bbox_strict_bounded": d["bbox"], "bbox_gt2d_extended": d["bbox"]}
+    batch = {"root": dict(view, images=u8(d["x_root"])),
+             "other": dict(view, images=u8(d["x_reg"]), keypoints_3d=kp3d, keypoints_2d=point_projection_from_3d_tensor(d["K"], kp3d),
+                           valid_mask_crop=torch.ones(B, kp3d.shape[1], device=DEV)),
+             "TCO": TCO, "K_original": K_original.repeat(B, 1, 1), "image_id": torch.arange(B),
+             "images_original": images_original_255 if images_original_255 is not None else torch.zeros(B, 3, 8, 8, device=DEV),
+             "jointpose": {n: d["q"][:, j] for j, n in enumerate(JOINT_NAMES["panda"])}}
+    args = types.SimpleNamespace(reference_keypoint_id=3, train_ds_names="synth", image_size=256.0, mask_loss_func="mse_mean",
+                                 mask_loss_weight=weights["mask"], iou_loss_weight=weights["iou"], scale_loss_weight=weights["scale"],
+                                 align_3d_loss_weight=weights["align"])
+    assert S.renderer_for(robot, K_original, DEV) is renderer
+    wrapped = _OffsetTrans(model, t_off)
+    meters = S.TrainMeters(DEV)
+    state = {"n": 0}
+
+    def target_net(images):                   # the mask network runs in every step, whichever target the loss takes (see the module docstring)
+        out = seg_net(images) if seg_net is not None else None
+        return out if a.mask_target == "net" and out is not None else seg[:, None]
+
+    def step():
+        loss, _ = S.farward_loss(args, batch, DEV, wrapped, robot, target_net, train=True, meters=meters)
+        opt.zero_grad()
+        loss.backward()
+        opt.step()
+        state["n"] += 1
+        if state["n"] % 10 == 0:
+            meters.read_and_reset()
+        return loss
+
+    def coverage():
+        with torch.no_grad():
+            out = wrapped(batch["other"]["images"], batch["root"]["images"], step.kv, K=d["K"])
+            return robot.get_rendered_masks(out[0], out[1], out[2], renderer, root=3).mean()
+    from hrpe_amd.lib.core.function import compute_k_values
+    step.kv = compute_k_values(d["K"][:, 0, 0], d["K"][:, 1, 1], d["bbox"])
+    step.meters, step.coverage = meters, coverage
+    return step
 
 
 def run(a, check=False):
@@ -86,7 +156,12 @@ def run(a, check=False):
     kv = compute_k_values(K[:, 0, 0], K[:, 1, 1], d["bbox"])
     mesh = grid_box_mesh(a.faces_per_side)
     K_original = torch.tensor([[640.0, 0, 320.0], [0, 640.0, 240.0], [0, 0, 1.0]])
-    renderer = model.robot.set_robot_renderer(K_original, original_image_size=(480, 640), scale=0.5, device=DEV, mesh=mesh)
+    library = getattr(a, "library_step", False)
+    if library:             # farward_loss asks renderer_for for this camera's renderer in every step: the one built here
+        from hrpe_amd.lib.core.sim2real import renderer_for
+        renderer = renderer_for(model.robot, K_original, DEV, mesh=mesh, scale=0.5, original_image_size=(480, 640))
+    else:
+        renderer = model.robot.set_robot_renderer(K_original, original_image_size=(480, 640), scale=0.5, device=DEV, mesh=mesh)
     opt = FusedClipAdam([p for p in model.parameters() if p.requires_grad], lr=1e-6, max_norm=5.0)
     with torch.no_grad():
         pose, rot, trans = model(d["x_reg"], d["x_root"], kv, K)[:3]
@@ -105,9 +180,21 @@ def run(a, check=False):
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(7)]
     acc = np.zeros(6)
     cover = 0.0
+    step_ms = []
+    if library:
+        lib_step = library_step(a, model, d, K_original, renderer, t_off, seg, seg_net, images_original_255 if seg_net is not None else None,
+                                weights, opt)
 
     def step(timed):
         nonlocal cover
+        if library:
+            ev[0].record()
+            loss = lib_step()
+            ev[6].record()
+            if timed:
+                torch.cuda.synchronize()
+                step_ms.append(ev[0].elapsed_time(ev[6]))
+            return loss
         ev[0].record()
         target = seg
         if seg_net is not None:
@@ -129,6 +216,7 @@ def run(a, check=False):
         if timed:
             torch.cuda.synchronize()
             acc[:] += [ev[i].elapsed_time(ev[i + 1]) for i in range(6)]
+            step_ms.append(ev[0].elapsed_time(ev[6]))
             cover = float(rendered.detach().mean())
         return loss
 
@@ -145,7 +233,12 @@ def run(a, check=False):
     ms = t0.elapsed_time(t1) / a.steps
     names = ["mask network (resize + DeepLabv3-ResNet50 + upsample)", "network forward", "mesh posing + rasteriser", "mask losses",
              "backward (losses, rasteriser, network)", "clip + Adam"]
-    extra = {}
+    extra = {"step_ms": {"median": round(float(np.median(step_ms)), 3), "min": round(min(step_ms), 3), "max": round(max(step_ms), 3),
+                         "n": len(step_ms)}} if step_ms else {}
+    if library:
+        extra["library_step"] = True
+        extra["meters"] = {k: round(v, 6) for k, v in lib_step.meters.read()[0].items()}
+        names, cover = [], float(lib_step.coverage())
     if check:
         with torch.no_grad():
             out = model(d["x_reg"], d["x_root"], kv, K)
@@ -157,9 +250,9 @@ def run(a, check=False):
             gs = [p.grad.float() for k, p in model.named_parameters() if k.startswith(pre) and p.grad is not None]
             gn[name] = float(torch.sqrt(sum((g_ * g_).sum() for g_ in gs))) if gs else 0.0
             gn[name + "_finite"] = all(bool(torch.isfinite(g_).all()) for g_ in gs)
-        extra = {"grad_norms": gn, "max_faces_per_pixel": int(model.robot.last_faces_per_pixel),
-                 "seg_mask_shape": list(seg_net(images_original_255).shape) if seg_net is not None else None,
-                 "rendered_shape": list(seg.shape)}
+        extra.update({"grad_norms": gn, "max_faces_per_pixel": int(model.robot.last_faces_per_pixel),
+                      "seg_mask_shape": list(seg_net(images_original_255).shape) if seg_net is not None else None,
+                      "rendered_shape": list(seg.shape)})
     return dict({"workload": "self-supervised render-and-compare step (BASELINE config 5) on synthetic meshes / images, plans replayed "
                                   "from HIP graphs, full network bf16 with frozen BatchNorm, mask network on 480x640 images, 240x320 masks",
                       "batch": B, "images_per_sec": round(B / ms * 1e3, 1),
