@@ -9,11 +9,14 @@ top of those pieces.  The model call itself is ``model(images, k_values)`` exact
 
 It differs from ``lib/core/function.py`` where the reference's two trainers differ: the ground truth comes from the ROOT view
 (``input_batch["root"]["keypoints_3d"]`` / ``["valid_mask_crop"]``, :172-174) and ``k_values`` takes ``abs(fx) * abs(fy)`` (:212)."""
+import functools
 import types
 
 import numpy as np
 import torch
 
+from hrpe_amd.lib.core.common import (compute_k_values, grown, images_to_device, loader_capacity, meter_mean, opt, select_bbox_and_K,
+                                      to_device, validation_batches)
 from hrpe_amd.lib.dataset.const import LINK_NAMES
 
 DEPTH_LOSS_FUNCS = ("l1", "mse")        # train_depthnet.py:249-254, 263-268
@@ -21,17 +24,9 @@ XY_LOSS_FUNCS = ("l1", "mse")           # :256-261
 VAL_TAGS = ("Val/rootz_loss", "Val/mean_depth_error", "Val/mean_x_error", "Val/mean_y_error")       # :298-301
 
 
-def _opt(args, name, default=None):
-    try:
-        return getattr(args, name)
-    except (AttributeError, KeyError):
-        return default
-
-
 def compute_depthnet_k_values(fx, fy, bboxes, real_bbox=(1000.0, 1000.0)):
     """k = sqrt(|fx| * |fy| * 1000 * 1000 / max(|x2-x1|, |y2-y1|)^2) in the reference's order of operations (:202-212)."""
-    area = torch.max(torch.abs(bboxes[:, 2] - bboxes[:, 0]), torch.abs(bboxes[:, 3] - bboxes[:, 1])) ** 2
-    return torch.sqrt(torch.abs(fx) * torch.abs(fy) * real_bbox[0] * real_bbox[1] / area).to(torch.float32)
+    return compute_k_values(fx, fy, bboxes, real_bbox, absolute=True)
 
 
 def prepare_depthnet_batch(input_batch, robot, device, reference_keypoint_id=3, use_origin_bbox=False, use_extended_bbox=True,
@@ -45,19 +40,11 @@ def prepare_depthnet_batch(input_batch, robot, device, reference_keypoint_id=3, 
     (:247).  With ``multi_kp``, ``gt["kp_depths"]`` = ``kp3d[:, kps_need_depth, 2]`` (:196-197) is there as well (a view for the host
     path; the kernel gathers it itself)."""
 
-    def dev(t, dtype=torch.float32):
-        return torch.as_tensor(t).to(device=device, dtype=dtype, non_blocking=True)
-
+    dev = functools.partial(to_device, device=device)
     root = input_batch["root"]
-    images = torch.as_tensor(root["images"])
-    images = images.to(device, non_blocking=True) if images.dtype == torch.uint8 else dev(images) / 255.      # :161
+    images = images_to_device(root["images"], device)                                                         # :161
     K = dev(root["K"])                                                                                        # :163
-    if use_extended_bbox:                                                                                     # :165-170, 203-208
-        bboxes, Kk = dev(root["bbox_gt2d_extended"]), K
-    elif use_origin_bbox:
-        bboxes, Kk = dev(input_batch["bbox_strict_bounded_original"]), dev(input_batch["K_original"])
-    else:
-        bboxes, Kk = dev(root["bbox_strict_bounded"]), K
+    bboxes, Kk = select_bbox_and_K(input_batch, root, K, device, use_origin_bbox, use_extended_bbox)          # :165-170, 203-208
     kp3d = dev(root["keypoints_3d"])                                                                          # :172
     valid_mask_crop = dev(root["valid_mask_crop"])                                                            # :174
     ref = int(reference_keypoint_id)
@@ -149,16 +136,10 @@ class DepthEvaluator:
 
     def reserve(self, B):
         """Make room for one more batch of B images -> (offset, batch index)."""
-        if self.count + B > self.capacity:
-            cap = max(self.count + B, 2 * self.capacity)
-            new = torch.zeros(3, cap, dtype=torch.float32, device=self.device)
-            new[:, :self.count].copy_(self.errors[:, :self.count])
-            self.errors, self.capacity = new, cap
-        if self.batches + 1 > self.batch_capacity:
-            cap = 2 * self.batch_capacity
-            new = torch.zeros(cap, dtype=torch.float32, device=self.device)
-            new[:self.batches].copy_(self.losses[:self.batches])
-            self.losses, self.batch_capacity = new, cap
+        if self.count + B > self.capacity or self.batches + 1 > self.batch_capacity:
+            self.errors = grown(self.errors, 1, self.count, self.count + B)
+            self.losses = grown(self.losses, 0, self.batches, self.batches + 1)
+            self.capacity, self.batch_capacity = self.errors.shape[1], self.losses.shape[0]
         return self.count, self.batches
 
     def commit(self, B):
@@ -186,10 +167,7 @@ class DepthEvaluator:
         n, nb = self.count, self.batches
         assert n > 0 and nb > 0, "DepthEvaluator.summary: nothing was added"
         errors, losses = self.errors[:, :n].cpu().numpy(), self.losses[:nb].cpu().numpy()
-        acc = 0.0
-        for v in losses:
-            acc += float(v)
-        return dict(rootz_loss=acc / nb, mean_depth_error=float(np.mean(errors[0])), mean_x_error=float(np.mean(errors[1])),
+        return dict(rootz_loss=float(meter_mean(losses)), mean_depth_error=float(np.mean(errors[0])), mean_x_error=float(np.mean(errors[1])),
                     mean_y_error=float(np.mean(errors[2])))
 
 
@@ -272,21 +250,21 @@ def farward_loss(args, input_batch, device, model, train=True, evaluator=None):
     ``prepare_depthnet_batch``, everything after the model call one hrp_depth_loss launch.  With an ``evaluator`` (validate passes
     the epoch's) the three errors are views of its rows; without one the errors of this batch alone are computed.  The model is
     called as it is (bring it to ``device`` - and wrap it for several GPUs, hrpe_amd.parallel - before)."""
-    xy = bool(_opt(args, "use_rootnet_xy_branch", False))
-    multi_kp = bool(_opt(args, "multi_kp", False))
-    depth_loss_func = _opt(args, "depth_loss_func", "l1")
-    xy_loss_func = _opt(args, "xy_loss_func", "mse") if xy else None
+    xy = bool(opt(args, "use_rootnet_xy_branch", False))
+    multi_kp = bool(opt(args, "multi_kp", False))
+    depth_loss_func = opt(args, "depth_loss_func", "l1")
+    xy_loss_func = opt(args, "xy_loss_func", "mse") if xy else None
     if xy and xy_loss_func is None:
         raise NotImplementedError("xy_loss_func=None with use_rootnet_xy_branch")
     kps = list(args.kps_need_depth) if multi_kp else None
     check_depthnet_options(depth_loss_func, xy_loss_func, kps)
     model.train() if train else model.eval()                                                                 # :153-156
     ref = int(args.reference_keypoint_id)
-    name = _opt(args, "urdf_robot_name", "panda")
+    name = opt(args, "urdf_robot_name", "panda")
     robot = types.SimpleNamespace(robot_type=name, link_names=LINK_NAMES[name])
     p = prepare_depthnet_batch(input_batch, robot, device, reference_keypoint_id=ref,
-                               use_origin_bbox=bool(_opt(args, "use_origin_bbox", False)),
-                               use_extended_bbox=bool(_opt(args, "use_extended_bbox", True)), multi_kp=multi_kp, kps_need_depth=kps)
+                               use_origin_bbox=bool(opt(args, "use_origin_bbox", False)),
+                               use_extended_bbox=bool(opt(args, "use_extended_bbox", True)), multi_kp=multi_kp, kps_need_depth=kps)
     pred = model(p["images"], p["k_values"])                                                                 # :221-231
     if train:
         return depthnet_loss(pred, p["gt"], depth_loss_func, xy_loss_func, kps, ref)
@@ -304,16 +282,9 @@ def validate(args, epoch, dsname, loader, model, writer, device):
     ``aug``) goes through ``DreamDataset.to_device`` first."""
     ds = "_" + dsname                                                                                        # :283
     model.eval()
-    dataset = getattr(loader, "dataset", None)
-    try:
-        capacity = len(dataset) if dataset is not None else 0
-    except TypeError:
-        capacity = 0
-    ev = DepthEvaluator(capacity or 1024, device=device)
+    ev = DepthEvaluator(loader_capacity(loader), device=device)
     with torch.no_grad():
-        for sample in loader:
-            if "frame" in sample and "aug" in sample:
-                sample = dataset.to_device(sample, device=device)
+        for sample in validation_batches(loader, device):
             farward_loss(args=args, input_batch=sample, device=device, model=model, train=False, evaluator=ev)
     s = ev.summary()
     if writer is not None:

@@ -10,23 +10,20 @@ projections go through the projection kernel.
 ``farward_loss`` (the reference's spelling) and ``validate`` are the reference's step and validation functions
 (function.py:19-327, 330-417) on top of those pieces; the metrics of a validation batch are one launch (hrp_eval_batch)
 into the device-side accumulators of an ``Evaluator``, read once per epoch."""
+import functools
 import math
 
-import numpy as np
 import torch
 
-from hrpe_amd.lib.dataset.const import INITIAL_JOINT_ANGLE, JOINT_NAMES, JOINT_TO_KP
+from hrpe_amd.lib.core.common import ADD_THRESHOLDS, PCK_THRESHOLDS  # noqa: F401  (module constants of this trainer as well)
+from hrpe_amd.lib.core.common import (compute_k_values, grown, images_to_device, loader_capacity, log_pose_validation, meter_mean, opt,
+                                      pose_step_inputs, select_bbox_and_K, to_device, validation_batches)
+from hrpe_amd.lib.dataset.const import JOINT_NAMES
 from hrpe_amd.lib.utils.geometries import rotmat_to_quat, rotmat_to_rot6d
 from hrpe_amd.lib.utils.transforms import point_projection_from_3d_tensor
 
 FULL_YAML_WEIGHTS = dict(pose=1.0, rot=1.0, trans=1.0, depth=10.0, uv=1.0, kp2d=10.0, kp3d=10.0,
                          kp2d_int=10.0, kp3d_int=10.0, align_3d=0.0)   # configs/panda/full.yaml:57-66
-
-
-def compute_k_values(fx, fy, bboxes, real_bbox=(1000.0, 1000.0)):
-    """k = sqrt(fx*fy*1000*1000 / max(|x2-x1|, |y2-y1|)^2)   (function.py:88-98)."""
-    area = torch.max(torch.abs(bboxes[:, 2] - bboxes[:, 0]), torch.abs(bboxes[:, 3] - bboxes[:, 1])) ** 2
-    return torch.sqrt(fx * fy * real_bbox[0] * real_bbox[1] / area).to(torch.float32)
 
 
 def prepare_batch(input_batch, robot, device, reference_keypoint_id=3, use_origin_bbox=False, use_extended_bbox=True,
@@ -43,17 +40,9 @@ def prepare_batch(input_batch, robot, device, reference_keypoint_id=3, use_origi
     the batch) of the annotated ``keypoints_2d_original`` against the FK key-points of the ground-truth joint angles under
     ``K_original[0]``; ``root_rot`` follows from it, ``trans`` stays TCO's."""
 
-    def dev(t, dtype=torch.float32):
-        return torch.as_tensor(t).to(device=device, dtype=dtype, non_blocking=True)
-
-    def images(t):
-        t = torch.as_tensor(t)
-        if t.dtype == torch.uint8:
-            return t.to(device, non_blocking=True)
-        return dev(t) / 255.
-
+    dev = functools.partial(to_device, device=device)
     root, other = input_batch["root"], input_batch["other"]
-    out = dict(root_images=images(root["images"]), reg_images=images(other["images"]),
+    out = dict(root_images=images_to_device(root["images"], device), reg_images=images_to_device(other["images"], device),
                root_K=dev(root["K"]), other_K=dev(other["K"]))
     TCO = dev(input_batch["TCO"])
     jp = input_batch["jointpose"]
@@ -73,12 +62,7 @@ def prepare_batch(input_batch, robot, device, reference_keypoint_id=3, use_origi
         assert reference_keypoint_id < len(robot.link_names), reference_keypoint_id
         root_trans = kp3d[:, reference_keypoint_id, :]
         root_rot = robot.get_rotation_at_specific_root(pose, rot, trans, root=reference_keypoint_id)
-    if use_extended_bbox:                                                                  # :43-48, 89-94
-        bboxes, Kk = dev(root["bbox_gt2d_extended"]), out["root_K"]
-    elif use_origin_bbox:
-        bboxes, Kk = dev(input_batch["bbox_strict_bounded_original"]), dev(input_batch["K_original"])
-    else:
-        bboxes, Kk = dev(root["bbox_strict_bounded"]), out["root_K"]
+    bboxes, Kk = select_bbox_and_K(input_batch, root, out["root_K"], device, use_origin_bbox, use_extended_bbox)   # :43-48, 89-94
     out["k_values"] = compute_k_values(Kk[:, 0, 0], Kk[:, 1, 1], bboxes)
     out["gt"] = dict(pose=pose, rot=rot, trans=trans, root_rot=root_rot, root_trans=root_trans,
                      root_depth=root_trans[:, 2:3], root_uv=kp2d[:, reference_keypoint_id, 0:2],
@@ -291,20 +275,13 @@ METRIC_KEYS = ("image_dis3d_avg", "image_dis2d_avg", "batch_dis3d_avg", "batch_d
                "batch_dis2d_avg_int", "root_depth_error_int", "rotation_diff")          # function.py:173-179
 
 
-def _opt(args, name, default=None):
-    try:
-        return getattr(args, name)
-    except (AttributeError, KeyError):
-        return default
-
-
 def check_loss_options(args):
     """NotImplementedError, naming the option, for what the fused loss does not cover (function.py:195-298)."""
     for name, shipped in SHIPPED_LOSS_FUNCS.items():
-        got = _opt(args, name, shipped)
+        got = opt(args, name, shipped)
         if got != shipped:
             raise NotImplementedError(f"{name}={got!r}: the fused loss implements {name}={shipped!r} (every configs/*/full.yaml)")
-    if _opt(args, "fix_mask", False):
+    if opt(args, "fix_mask", False):
         raise NotImplementedError("fix_mask=True: the fused loss has no masked kp3d_int / align_3d terms (function.py:276-278, 294-296)")
 
 
@@ -335,21 +312,12 @@ class Evaluator:
         self.losses = torch.zeros(self.batch_capacity, len(LOSS_SLOTS), **f)
 
     def _grow(self, images, batches):
-        if images > self.capacity:
-            cap = max(images, 2 * self.capacity)
-            new = torch.zeros(self.per_image.shape[0], cap, dtype=torch.float32, device=self.device)
-            new[:, :self.count].copy_(self.per_image[:, :self.count])
-            self.per_image, self.capacity = new, cap
-        if batches > self.batch_capacity:
-            cap, n = max(batches, 2 * self.batch_capacity), self.batches
-            for name, dim in (("dis", 1), ("l1_joint", 0), ("rot_diff", 0), ("losses", 0)):
-                old = getattr(self, name)
-                shape = list(old.shape)
-                shape[dim] = cap
-                new = torch.zeros(shape, dtype=torch.float32, device=self.device)
-                new.narrow(dim, 0, n).copy_(old.narrow(dim, 0, n))
-                setattr(self, name, new)
-            self.batch_capacity = cap
+        if images <= self.capacity and batches <= self.batch_capacity:
+            return
+        self.per_image = grown(self.per_image, 1, self.count, images)
+        for name, axis in (("dis", 1), ("l1_joint", 0), ("rot_diff", 0), ("losses", 0)):
+            setattr(self, name, grown(getattr(self, name), axis, self.batches, batches))
+        self.capacity, self.batch_capacity = self.per_image.shape[1], self.losses.shape[0]
 
     def add(self, pred, gt, loss=None, loss_dict=None):
         """pred: dict(kp3d_fk [B,nkp,3], kp3d_int [B,nkp,3], joint [B,dof] or None, rot [B,rot_dim]);
@@ -416,19 +384,13 @@ class Evaluator:
         out = summary_add_pck({"dis3d": im["error3d"], "dis2d": im["error2d"]})
         out["integral"] = summary_add_pck({"dis3d": im["error3d_int"], "dis2d": im["error2d_int"]})
         out["relative"] = summary_add_pck({"dis3d": im["error3d_relative"], "dis2d": im["error2d"]})
-
-        def meter(rows):                       # AverageValueMeter: sum of the added values / their number
-            acc = np.zeros(rows.shape[1:], np.float64)
-            for r in rows.double().numpy():
-                acc = acc + r
-            return acc / rows.shape[0]
-        losses = meter(self.losses[:nb].cpu())
+        losses = meter_mean(self.losses[:nb].cpu())
         dis = self.dis[:, :nb].cpu()
         meters = {k: float(losses[i]) for i, k in enumerate(LOSS_SLOTS)}
-        meters["rotation_diff"] = float(meter(self.rot_diff[:nb].cpu().reshape(nb, 1))[0])
+        meters["rotation_diff"] = float(meter_mean(self.rot_diff[:nb].cpu().reshape(nb, 1))[0])
         for i, k in enumerate(("dis3d", "dis2d", "dis3d_int", "dis2d_int")):
-            meters[k] = meter(dis[i])
-        meters["l1_joint"] = meter(self.l1_joint[:nb].cpu())
+            meters[k] = meter_mean(dis[i])
+        meters["l1_joint"] = meter_mean(self.l1_joint[:nb].cpu())
         out["meters"] = meters
         out["mean_joint_error"] = float(im["mean_jointerror"].double().mean()) / math.pi * 180.0
         out["mean_depth_error"] = float(im["error_depth"].double().mean())
@@ -445,56 +407,21 @@ def farward_loss(args, input_batch, model, robot, device, device_id, train=True,
     ``device`` and wrap it for several GPUs - hrpe_amd.parallel - before)."""
     check_loss_options(args)
     model.train() if train else model.eval()
-    root = int(args.reference_keypoint_id)
-    rotation_dim = int(_opt(args, "rotation_dim", 6))
-    p = prepare_batch(input_batch, robot, device, reference_keypoint_id=root, use_origin_bbox=bool(_opt(args, "use_origin_bbox", False)),
-                      use_extended_bbox=bool(_opt(args, "use_extended_bbox", True)),
-                      synthetic="synth" in args.train_ds_names, rotation_dim=rotation_dim)                # :66
-    gt = dict(p["gt"])
-    gt_pose_before_mask = gt["pose"]                                                                     # :107
-    if _opt(args, "use_joint_valid_mask", False):                                                        # :104-114
-        valid_mask = torch.as_tensor(input_batch["valid_mask"]).to(device=device, dtype=torch.float32)
-        joint_valid_mask = valid_mask[:, JOINT_TO_KP[robot.robot_type]]
-        assert joint_valid_mask.shape == gt["pose"].shape, (joint_valid_mask.shape, gt["pose"].shape)
-        mean_joints = torch.tensor([INITIAL_JOINT_ANGLE["mean"][robot.robot_type][k] for k in JOINT_NAMES[robot.robot_type]],
-                                   dtype=torch.float32, device=device).unsqueeze(0)
-        gt["pose"] = gt["pose"] * joint_valid_mask + mean_joints * (1 - joint_valid_mask)
-    pred = tuple(model(p["reg_images"], p["root_images"], p["k_values"], K=p["other_K"]))                # :115-120
-    multi_kp = bool(_opt(args, "multi_kp", False))
+    multi_kp = bool(opt(args, "multi_kp", False))
+    st = pose_step_inputs(args, input_batch, model, robot, device, int(opt(args, "rotation_dim", 6)), evaluate=not train)
+    p, gt, pred, pred_pose, root = st.p, st.gt, st.pred, st.pred_pose, st.root
     assert len(pred) == (9 if multi_kp else 8), len(pred)
-    pred_pose, pred_rot, pred_trans = pred[0], pred[1], pred[2]
-    if _opt(args, "known_joint", False):                                                                 # :124-125
+    if not train and evaluator is None:
+        evaluator = Evaluator(robot, pred_pose.shape[0], reference_keypoint_id=root, device=device, batch_capacity=1)
+    if opt(args, "known_joint", False):                                                                  # :188-189
         pred_pose = gt["pose"].clone()
-    metric_dict = None
-    if not train:                                                                                        # :137-179
-        if evaluator is None:
-            evaluator = Evaluator(robot, pred_pose.shape[0], reference_keypoint_id=root, device=device, batch_capacity=1)
-        with torch.no_grad():
-            kp3d_fk = robot.get_keypoints_root(pred_pose.detach().float(), pred_rot.detach().float(), pred_trans.detach().float(),
-                                               root=root)                                                # metrics.py:27-34
-        ev_pred = dict(kp3d_fk=kp3d_fk, kp3d_int=pred[-2], joint=pred_pose, rot=pred_rot)
-        # the reference's quirk, kept: rotation_diff compares pred_rot - the rotation at the ROOT key-point - with the BASE
-        # rotation gt_rot, not with gt_root_rot (function.py:169-172); the metrics use the unmasked joint angles (:145)
-        ev_gt = dict(kp3d=gt["kp3d"], kp2d_original=torch.as_tensor(input_batch["keypoints_2d_original"]),
-                     K_original=torch.as_tensor(input_batch["K_original"]), joint=gt_pose_before_mask, rot=gt["rot"])
-    jw = _opt(args, "joint_individual_weights")
-    if jw is not None:                                                                                   # :182-186
-        assert len(jw) == robot.dof
-        w = torch.tensor(list(jw), dtype=torch.float32, device=device).reshape(1, -1)
-        pred_pose, gt["pose"] = pred_pose * w, gt["pose"] * w
-    if _opt(args, "known_joint", False):                                                                 # :188-189
-        pred_pose = gt["pose"].clone()
-    weights = {k: float(_opt(args, k + "_loss_weight", FULL_YAML_WEIGHTS[k])) for k in _WEIGHT_KEYS}
-    loss, loss_dict = full_loss((pred_pose,) + pred[1:], gt, p["other_K"], root=root, image_size=float(_opt(args, "image_size", 256.0)),
-                                weights=weights, kps_need_depth=_opt(args, "kps_need_depth") if multi_kp else None)
+    weights = {k: float(opt(args, k + "_loss_weight", FULL_YAML_WEIGHTS[k])) for k in _WEIGHT_KEYS}
+    loss, loss_dict = full_loss((pred_pose,) + pred[1:], gt, p["other_K"], root=root, image_size=float(opt(args, "image_size", 256.0)),
+                                weights=weights, kps_need_depth=opt(args, "kps_need_depth") if multi_kp else None)
     if train:
         return loss, loss_dict
-    metric_dict = evaluator.add(ev_pred, ev_gt, loss, loss_dict)
+    metric_dict = evaluator.add(st.ev_pred, st.ev_gt, loss, loss_dict)
     return loss, loss_dict, metric_dict
-
-
-ADD_THRESHOLDS = [1, 5, 10, 20, 40, 60, 80, 100]                      # function.py:342-343
-PCK_THRESHOLDS = [2.5, 5.0, 7.5, 10.0, 12.5, 15.0, 17.5, 20.0]
 
 
 def validate(args, epoch, dsname, loader, model, robot, writer, device, device_id):
@@ -506,21 +433,14 @@ def validate(args, epoch, dsname, loader, model, robot, writer, device, device_i
     assert (dsname in ["dr", "photo"] or args.urdf_robot_name == "panda")   # ds != dr/photo -> panda
     ds = "_" + dsname
     model.eval()
-    dataset = getattr(loader, "dataset", None)
-    try:
-        capacity = len(dataset) if dataset is not None else 0
-    except TypeError:
-        capacity = 0
-    ev = Evaluator(robot, capacity or 1024, reference_keypoint_id=args.reference_keypoint_id, device=device)
+    ev = Evaluator(robot, loader_capacity(loader), reference_keypoint_id=args.reference_keypoint_id, device=device)
     with torch.no_grad():
-        for sample in loader:
-            if "frame" in sample and "aug" in sample:
-                sample = dataset.to_device(sample, device=device)
+        for sample in validation_batches(loader, device):
             farward_loss(args=args, input_batch=sample, model=model, robot=robot, device=device, device_id=device_id, train=False,
                          evaluator=ev)
     s = ev.summary()
     if writer is not None:
-        m, s_int = s["meters"], s["integral"]
+        m = s["meters"]
         add = lambda tag, v: writer.add_scalar(tag + ds, float(v), epoch)   # noqa: E731
         add("Val/loss", m["loss"])
         add("Val/pose_loss", m["loss_joint"])
@@ -535,24 +455,6 @@ def validate(args, epoch, dsname, loader, model, robot, writer, device, device_i
         add("Val/error2d_int_loss", m["loss_error2d"])
         add("Val/error3d_int_loss", m["loss_error3d"])
         add("Val/error3d_align_loss", m["loss_error3d_align"])
-        add("Val/mean_joint_error", s["mean_joint_error"])
-        add("Val/AUC_ADD", s["ADD/AUC"])
-        add("Val/AUC_PCK", s["PCK/AUC"])
-        add("Val/AUC_ADD_integral_xyz_metrics", s_int["ADD/AUC"])
-        add("Val/AUC_PCK_integral_xyz_metrics", s_int["PCK/AUC"])
-        for th in ADD_THRESHOLDS:
-            add(f"Val/ADD_{th}_mm", s[f"ADD_{th}_mm"])
-        for th in PCK_THRESHOLDS:
-            add(f"Val/PCK_{th}_pixel", s[f"PCK_{th}_pixel"])
-        for th in ADD_THRESHOLDS:
-            add(f"Val/ADD_{th}_mm_integral_xyz_metrics", s_int[f"ADD_{th}_mm"])
-        for th in PCK_THRESHOLDS:
-            add(f"Val/PCK_{th}_pixel_integral_xyz_metrics", s_int[f"PCK_{th}_pixel"])
-        for name, suffix in (("dis3d", ""), ("dis2d", ""), ("dis3d_int", "_integral_xyz_metrics"), ("dis2d_int", "_integral_xyz_metrics")):
-            kind = "3D" if name.startswith("dis3d") else "2D"
-            for k in range(ev.nkp):
-                add(f"Val/distance{kind}_keypoint_{k + 1}{suffix}", m[name][k])
-        for k in range(ev.dof):
-            add(f"Val/l1error_joint_{k + 1}", m["l1_joint"][k])
+        log_pose_validation(add, s, ev.nkp, ev.dof, integral_details=True)
     model.train()
     return s["ADD/AUC"]

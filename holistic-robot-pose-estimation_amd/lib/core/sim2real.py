@@ -27,8 +27,7 @@ import torch
 
 from hrpe_amd import _native as nv
 from hrpe_amd.lib.core import function as F
-from hrpe_amd.lib.core.function import _opt
-from hrpe_amd.lib.dataset.const import INITIAL_JOINT_ANGLE, JOINT_NAMES, JOINT_TO_KP
+from hrpe_amd.lib.core.common import grown, loader_capacity, log_pose_validation, meter_mean, opt, pose_step_inputs, validation_batches
 
 ROW = nv.SIM2REAL_ROW                   # the twelve values of one step, in hrp_sim2real_monitor's order
 LOSS_KEYS = ("loss_joint", "loss_rot", "loss_uv", "loss_depth", "loss_trans", "loss_error2d", "loss_error3d", "loss_mask", "loss_scale",
@@ -45,14 +44,14 @@ def check_sim2real_options(args):
     """NotImplementedError, naming the option, for what the step does not cover: a loss function outside the shipped ones
     (train_sim2real.py:317-388, 435-442) and the 5-tuple model branch (:244-251)."""
     for name, shipped in SHIPPED_LOSS_FUNCS.items():
-        got = _opt(args, name, shipped)
+        got = opt(args, name, shipped)
         if got != shipped:
             raise NotImplementedError(f"{name}={got!r}: the monitor kernel implements {name}={shipped!r} "
                                       "(every configs/*/self_supervised/*.yaml)")
-    got = _opt(args, "mask_loss_func", "mse_mean")
+    got = opt(args, "mask_loss_func", "mse_mean")
     if got not in MASK_LOSS_FUNCS:
         raise NotImplementedError(f"mask_loss_func={got!r}: the mask loss implements {MASK_LOSS_FUNCS}")
-    flags = [_opt(args, n) for n in MODEL_OPTIONS]
+    flags = [opt(args, n) for n in MODEL_OPTIONS]
     if any(f is not None for f in flags) and not any(flags):
         raise NotImplementedError(f"{MODEL_OPTIONS[0]}=False and {MODEL_OPTIONS[1]}=False: the 5-tuple model branch "
                                   "(train_sim2real.py:244-251) is not built; the step takes an 8-tuple model")
@@ -215,14 +214,8 @@ class Sim2RealEvaluator:
     def reserve(self, B):
         """Make room for one more batch of B images -> the row of ``rows`` that batch owns."""
         n, nb = self.ev.count, self.ev.batches
-        if n + B > self.image_ids.shape[0]:
-            new = torch.zeros(max(n + B, 2 * self.image_ids.shape[0]), dtype=torch.int64, device=self.device)
-            new[:n].copy_(self.image_ids[:n])
-            self.image_ids = new
-        if nb + 1 > self.rows.shape[0]:
-            new = torch.zeros(max(nb + 1, 2 * self.rows.shape[0]), 12, dtype=torch.float32, device=self.device)
-            new[:nb].copy_(self.rows[:nb])
-            self.rows = new
+        self.image_ids = grown(self.image_ids, 0, n, n + B)
+        self.rows = grown(self.rows, 0, nb, nb + 1)
         return nb
 
     def add(self, pred, gt, image_id):
@@ -260,10 +253,8 @@ class Sim2RealEvaluator:
         ids, rows = self._host()
         s = self.ev.summary()
         out = {k: v for k, v in s.items() if k not in ("meters", "relative", "mean_depth_error", "relative_depth_error", "Relative_ADD/AUC")}
-        acc = np.zeros(12, np.float64)
-        for r in rows:
-            acc = acc + r
-        meters = {k: float(acc[i] / rows.shape[0]) for i, k in enumerate(ROW)}
+        means = meter_mean(rows)
+        meters = {k: float(means[i]) for i, k in enumerate(ROW)}
         for k in ("rotation_diff", "dis3d", "dis2d", "dis3d_int", "dis2d_int", "l1_joint"):
             meters[k] = s["meters"][k]
         out["meters"] = meters
@@ -341,61 +332,31 @@ def farward_loss(args, input_batch, device, model, robot, seg_net, train=True, e
     is called as it is (bring it to ``device`` - and wrap it for several GPUs, hrpe_amd.parallel - before)."""
     check_sim2real_options(args)
     set_step_modes(model, train)                                                                         # :139-146
-    root = int(args.reference_keypoint_id)
-    p = F.prepare_batch(input_batch, robot, device, reference_keypoint_id=root, use_origin_bbox=bool(_opt(args, "use_origin_bbox", False)),
-                        use_extended_bbox=bool(_opt(args, "use_extended_bbox", True)),
-                        synthetic="synth" in args.train_ds_names, rotation_dim=6)                         # :151-221
-    gt = dict(p["gt"])
-    gt_pose_before_mask = gt["pose"]                                                                     # :230
-    if _opt(args, "use_joint_valid_mask", False):                                                        # :232-237
-        valid_mask = torch.as_tensor(input_batch["valid_mask"]).to(device=device, dtype=torch.float32)
-        joint_valid_mask = valid_mask[:, JOINT_TO_KP[robot.robot_type]]
-        assert joint_valid_mask.shape == gt["pose"].shape, (joint_valid_mask.shape, gt["pose"].shape)
-        mean_joints = torch.tensor([INITIAL_JOINT_ANGLE["mean"][robot.robot_type][k] for k in JOINT_NAMES[robot.robot_type]],
-                                   dtype=torch.float32, device=device).unsqueeze(0)
-        gt["pose"] = gt["pose"] * joint_valid_mask + mean_joints * (1 - joint_valid_mask)
-    pred = tuple(model(p["reg_images"], p["root_images"], p["k_values"], K=p["other_K"]))                # :239-241
+    st = pose_step_inputs(args, input_batch, model, robot, device, rotation_dim=6, evaluate=not train)   # :151-311
+    p, gt, pred, pred_pose, root = st.p, st.gt, st.pred, st.pred_pose, st.root
     if len(pred) != 8:
         raise NotImplementedError(f"the model returned {len(pred)} values: the 5-tuple model branch (train_sim2real.py:244-251, "
                                   f"{MODEL_OPTIONS[0]}=False and {MODEL_OPTIONS[1]}=False) is not built; the step takes an 8-tuple model")
-    pred_pose, pred_rot, pred_trans = pred[0], pred[1], pred[2]
-    known_joint = bool(_opt(args, "known_joint", False))
-    if known_joint:                                                                                      # :253-254
-        pred_pose = gt["pose"].clone()
+    mon_pred = (pred_pose,) + pred[1:]
+    image_size = float(opt(args, "image_size", 256.0))
     if not train:                                                                                        # :265-304
         B = pred_pose.shape[0]
         if evaluator is None:
             evaluator = Sim2RealEvaluator(robot, B, reference_keypoint_id=root, device=device, batch_capacity=1)
-        with torch.no_grad():
-            kp3d_fk = robot.get_keypoints_root(pred_pose.detach().float(), pred_rot.detach().float(), pred_trans.detach().float(),
-                                               root=root)                                                # metrics.py:27-34
-        ev_pred = dict(kp3d_fk=kp3d_fk, kp3d_int=pred[6], joint=pred_pose, rot=pred_rot)
-        # the reference's quirk, kept: rotation_diff compares pred_rot - the rotation at the ROOT key-point - with the BASE
-        # rotation gt_rot, not with gt_root_rot (:298); the metrics use the unmasked joint angles (:272)
-        ev_gt = dict(kp3d=gt["kp3d"], kp2d_original=torch.as_tensor(input_batch["keypoints_2d_original"]),
-                     K_original=torch.as_tensor(input_batch["K_original"]), joint=gt_pose_before_mask, rot=gt["rot"])
-    jw = _opt(args, "joint_individual_weights")
-    if jw is not None:                                                                                   # :307-311
-        assert len(jw) == robot.dof
-        w = torch.tensor(list(jw), dtype=torch.float32, device=device).reshape(1, -1)
-        pred_pose, gt["pose"] = pred_pose * w, gt["pose"] * w
-    mon_pred = (pred_pose,) + pred[1:]
-    image_size = float(_opt(args, "image_size", 256.0))
-    if not train:
         row_index = evaluator.reserve(B)                  # (may reallocate evaluator.rows)
         row, terms = sim2real_monitor(mon_pred, gt, p["other_K"], image_size, mask_terms=None, rows=evaluator.rows, row_index=row_index)
-        metric_dict = evaluator.add(ev_pred, ev_gt, input_batch["image_id"])
+        metric_dict = evaluator.add(st.ev_pred, st.ev_gt, input_batch["image_id"])
         return row[0], {k: terms[k] for k in LOSS_KEYS}, metric_dict                                     # :402, 534
-    if known_joint:                                                                                      # :404-405
+    if opt(args, "known_joint", False):                                                                  # :404-405
         pred_pose = gt["pose"].clone()
     images_original = torch.as_tensor(input_batch["images_original"]).to(device, non_blocking=True)
     images_original_255 = images_original.float()        # :158-159 (x / 255 * 255 of a 0..255 value)
     K0 = torch.as_tensor(input_batch["K_original"])[0]
     renderer = renderer_for(robot, K0, device)                                                           # :406-408
     seg_masks = seg_net(images_original_255).detach()                                                    # :412
-    rendered_masks = robot.get_rendered_masks(pred_pose, pred_rot, pred_trans, renderer, root=root)      # :414-416, 434
-    weights = {k: float(_opt(args, name, F.SIM2REAL_YAML_WEIGHTS[k])) for k, name in _WEIGHT_OPTIONS.items()}
-    loss, mterms = F.sim2real_mask_loss(rendered_masks, seg_masks, pred[7], pred[6], _opt(args, "mask_loss_func", "mse_mean"),
+    rendered_masks = robot.get_rendered_masks(pred_pose, pred[1], pred[2], renderer, root=root)          # :414-416, 434
+    weights = {k: float(opt(args, name, F.SIM2REAL_YAML_WEIGHTS[k])) for k, name in _WEIGHT_OPTIONS.items()}
+    loss, mterms = F.sim2real_mask_loss(rendered_masks, seg_masks, pred[7], pred[6], opt(args, "mask_loss_func", "mse_mean"),
                                         weights)                                                         # :435-468
     _, terms = sim2real_monitor(mon_pred, gt, p["other_K"], image_size, mask_terms=_mask_terms(loss, mterms), meters=meters)
     return loss, {k: terms[k] for k in LOSS_KEYS}                                                        # :532
@@ -421,16 +382,9 @@ def validate(args, epoch_log, dsname, loader, model, robot, seg_net, writer, dev
         assert dsname in args.train_ds_names, dsname                                                     # :537-539
     ds = "_" + dsname
     model.eval()
-    dataset = getattr(loader, "dataset", None)
-    try:
-        capacity = len(dataset) if dataset is not None else 0
-    except TypeError:
-        capacity = 0
-    ev = Sim2RealEvaluator(robot, capacity or 1024, reference_keypoint_id=args.reference_keypoint_id, device=device)
+    ev = Sim2RealEvaluator(robot, loader_capacity(loader), reference_keypoint_id=args.reference_keypoint_id, device=device)
     with torch.no_grad():
-        for sample in loader:
-            if "frame" in sample and "aug" in sample:
-                sample = dataset.to_device(sample, device=device)
+        for sample in validation_batches(loader, device):
             farward_loss(args=args, input_batch=sample, device=device, model=model, robot=robot, seg_net=seg_net, train=False,
                          evaluator=ev)
     model.train()                                                                                        # :624
@@ -438,7 +392,7 @@ def validate(args, epoch_log, dsname, loader, model, robot, seg_net, writer, dev
         return ev.worst_cases()
     s = ev.summary()
     if writer is not None:
-        m, s_int = s["meters"], s["integral"]
+        m = s["meters"]
         at = epoch_log if epoch is None else epoch
         add = lambda tag, v, e=epoch_log: writer.add_scalar(tag + ds, float(v), e)   # noqa: E731
         add("Val/loss", m["loss"])                                                                       # :597-608
@@ -453,19 +407,5 @@ def validate(args, epoch_log, dsname, loader, model, robot, seg_net, writer, dev
         add("Val/depth_loss", m["loss_depth"])
         add("Val/error2d_loss", m["loss_error2d"])
         add("Val/error3d_loss", m["loss_error3d"])
-        add("Val/mean_joint_error", s["mean_joint_error"])                                               # :609-613
-        add("Val/AUC_ADD", s["ADD/AUC"])
-        add("Val/AUC_PCK", s["PCK/AUC"])
-        add("Val/AUC_ADD_integral_xyz_metrics", s_int["ADD/AUC"], at)
-        add("Val/AUC_PCK_integral_xyz_metrics", s_int["PCK/AUC"], at)
-        for th in ADD_THRESHOLDS:                                                                        # :614-617
-            add(f"Val/ADD_{th}_mm", s[f"ADD_{th}_mm"])
-        for th in PCK_THRESHOLDS:
-            add(f"Val/PCK_{th}_pixel", s[f"PCK_{th}_pixel"])
-        for k in range(ev.nkp):                                                                          # :618-623
-            add(f"Val/distance3D_keypoint_{k + 1}", m["dis3d"][k])
-        for k in range(ev.nkp):
-            add(f"Val/distance2D_keypoint_{k + 1}", m["dis2d"][k])
-        for k in range(ev.dof):
-            add(f"Val/l1error_joint_{k + 1}", m["l1_joint"][k])
+        log_pose_validation(add, s, ev.nkp, ev.dof, integral_details=False, integral_epoch=at)           # :609-623
     return s["ADD/AUC"], s["meters"]["loss"]
