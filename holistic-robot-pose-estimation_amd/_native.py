@@ -308,6 +308,7 @@ PROTOTYPES = {
     "hrp_conv2d_fwd": [C.POINTER(ConvDesc), _P],
     "hrp_conv_rowstrip_channels": [C.POINTER(ConvDesc)],
     "hrp_conv_pointwise": [C.POINTER(ConvDesc)],
+    "hrp_conv_tile_config": [C.POINTER(ConvDesc)],
     "hrp_conv2d_bwd_weight": [C.POINTER(WgradDesc), _P],
     "hrp_colsum": [_P, _I, _L, _I, _I, _P, _I, _P, _L, _P],
     "hrp_colsum_workspace_bytes": [_L, _I],

@@ -52,6 +52,16 @@ extern "C" int hrp_conv_pointwise(const hrp_conv_desc* d) {
   return d ? hrp::pw_plan(*d, pw) : 0;
 }
 
+extern "C" int hrp_conv_tile_config(const hrp_conv_desc* d) {
+  using namespace hrp;
+  if (!d || conv_check(d) != HRP_OK) return 0;
+  if (d->dtype == HRP_F32) return conv_tile_config<float>(*d);
+  if (d->dtype == HRP_F32X3) return conv_tile_config<f32x3_t>(*d);
+  PwPlan pw;
+  if (hrp_conv_rowstrip_channels(d) || pw_plan(*d, pw)) return 0;
+  return conv_tile_config<bf16_t>(*d);
+}
+
 extern "C" int hrp_conv2d_fwd(const hrp_conv_desc* d, void* stream) {
   using namespace hrp;
   const int rc = conv_check(d);

@@ -805,13 +805,10 @@ static int plan_cfg(const hrp_conv_desc& d, ConvTiling& t, int& lds_out, bool al
   return HRP_OK;
 }
 
+// Launch of one problem on the tile configuration (and with the tiling) that choose_conv_nt settled on.
 template <typename T, int CT, int PT, int WC, int WP, int NT>
-static int launch_cfg(const hrp_conv_desc& d, hipStream_t s) {
+static int launch_cfg(const hrp_conv_desc& d, const ConvTiling& t, const int lds, hipStream_t s) {
   constexpr int SZ = Elem<T>::SZ;
-  ConvTiling t;
-  int lds = 0;
-  const int prc = plan_cfg<T, CT, PT, WC, WP, NT>(d, t, lds, true);
-  if (prc != HRP_OK) return prc;
   // persistent workgroups (about two per CU, each walking tiles b, b + grid, ...) when a tile is little MFMA
   // work and there are several tiles per CU; one tile per workgroup otherwise
   const int mfma_per_tile = cdiv(d.Cin * SZ, ROW) * NT * CT * PT * Mma<T>::KSTEPS;
@@ -843,11 +840,26 @@ static int launch_cfg(const hrp_conv_desc& d, hipStream_t s) {
   return check_launch("conv_tile_kernel");
 }
 
-// Tile choice.  Weight bytes streamed per workgroup are fixed by BN x K, so the pixel tile should be as
-// large as the launch allows while still giving every CU a workgroup (>= 256 blocks); BN = 64 at most so
-// that two stage buffers of a 3x3 conv stay under ~60 KB.
+// What the candidate walk settled on for one problem: the configuration as CT * 1000 + PT * 100 + WC * 10 + WP (the number
+// hrp_conv_tile_config reports), its tiling and its LDS bytes.
+struct ConvChoice {
+  int cfg;
+  ConvTiling t;
+  int lds;
+};
+
+template <typename T, int CT, int PT, int WC, int WP, int NT>
+static int try_cfg(const hrp_conv_desc& d, ConvChoice& c) {
+  c.cfg = CT * 1000 + PT * 100 + WC * 10 + WP;
+  return plan_cfg<T, CT, PT, WC, WP, NT>(d, c.t, c.lds, true);
+}
+
+// Tile choice (host only, no HIP call: launch_conv_nt launches what it returns, hrp_conv_tile_config reports it).  Weight bytes
+// streamed per workgroup are fixed by BN x K, so the pixel tile should be as large as the launch allows while still giving
+// every CU a workgroup (>= 256 blocks); BN = 64 at most so that two stage buffers of a 3x3 conv stay under ~60 KB.
+// -> HRP_OK, -100 (no configuration fits; g_conv_border_reject says why) or HRP_ERR_ARG.
 template <typename T, int NT>
-static int launch_conv_nt(const hrp_conv_desc& d, hipStream_t s) {
+static int choose_conv_nt(const hrp_conv_desc& d, ConvChoice& c) {
   const long pixels = (long)d.N * d.Ho * d.Wo;
   static const long want = 256;
   static const int low_kb = 76;
@@ -857,18 +869,25 @@ static int launch_conv_nt(const hrp_conv_desc& d, hipStream_t s) {
   g_conv_lds_budget_kb = pass == 0 ? low_kb : 76;
   if (pass == 1 && low_kb >= 76) break;
   if (d.Cout <= 32) {
-    if (pixels / 256 >= want) rc = launch_cfg<T, 1, 2, 1, 4, NT>(d, s);
-    if (rc == -100) rc = launch_cfg<T, 1, 1, 1, 4, NT>(d, s);
+    if (pixels / 256 >= want) rc = try_cfg<T, 1, 2, 1, 4, NT>(d, c);
+    if (rc == -100) rc = try_cfg<T, 1, 1, 1, 4, NT>(d, c);
   } else {
     const long nb = (d.Cout + 63) / 64;
-    if (pixels / 256 * nb >= want) rc = launch_cfg<T, 2, 2, 1, 4, NT>(d, s);
-    if (rc == -100 && pixels / 128 * nb >= want) rc = launch_cfg<T, 2, 1, 1, 4, NT>(d, s);
-    if (rc == -100) rc = launch_cfg<T, 1, 1, 2, 2, NT>(d, s);
-    if (rc == -100) rc = launch_cfg<T, 2, 1, 1, 4, NT>(d, s);
-    if (rc == -100) rc = launch_cfg<T, 1, 1, 1, 4, NT>(d, s);   // 32 couts per workgroup: halves the weight slab (16-tap kernels)
+    if (pixels / 256 * nb >= want) rc = try_cfg<T, 2, 2, 1, 4, NT>(d, c);
+    if (rc == -100 && pixels / 128 * nb >= want) rc = try_cfg<T, 2, 1, 1, 4, NT>(d, c);
+    if (rc == -100) rc = try_cfg<T, 1, 1, 2, 2, NT>(d, c);
+    if (rc == -100) rc = try_cfg<T, 2, 1, 1, 4, NT>(d, c);
+    if (rc == -100) rc = try_cfg<T, 1, 1, 1, 4, NT>(d, c);   // 32 couts per workgroup: halves the weight slab (16-tap kernels)
   }
   }
   g_conv_lds_budget_kb = 76;
+  return rc;
+}
+
+template <typename T, int NT>
+static int launch_conv_nt(const hrp_conv_desc& d, hipStream_t s) {
+  ConvChoice c;
+  const int rc = choose_conv_nt<T, NT>(d, c);
   if (rc == -100) {
     if (g_conv_border_reject)
       set_error("conv: no tile configuration fits: the tap offsets reach beyond the border tiles of every tile that fits LDS "
@@ -877,7 +896,30 @@ static int launch_conv_nt(const hrp_conv_desc& d, hipStream_t s) {
       set_error("conv: tile does not fit LDS (H=%d W=%d Cin=%d stride=%d taps=%d)", d.H, d.W, d.Cin, d.in_stride, d.ntaps);
     return HRP_ERR_ARG;
   }
-  return rc;
+  if (rc != HRP_OK) return rc;
+  switch (c.cfg) {
+    case 1214: return launch_cfg<T, 1, 2, 1, 4, NT>(d, c.t, c.lds, s);
+    case 1114: return launch_cfg<T, 1, 1, 1, 4, NT>(d, c.t, c.lds, s);
+    case 2214: return launch_cfg<T, 2, 2, 1, 4, NT>(d, c.t, c.lds, s);
+    case 2114: return launch_cfg<T, 2, 1, 1, 4, NT>(d, c.t, c.lds, s);
+    default: return launch_cfg<T, 1, 1, 2, 2, NT>(d, c.t, c.lds, s);
+  }
+}
+
+// hrp_conv_tile_config for element type T: the configuration launch_conv<T> would run, + 10000 with split-K; 0: none fits.
+template <typename T>
+static int conv_tile_config(const hrp_conv_desc& d) {
+  ConvChoice c;
+  int rc;
+  switch (d.ntaps) {
+    case 1: rc = choose_conv_nt<T, 1>(d, c); break;
+    case 2: rc = choose_conv_nt<T, 2>(d, c); break;
+    case 4: rc = choose_conv_nt<T, 4>(d, c); break;
+    case 9: rc = choose_conv_nt<T, 9>(d, c); break;
+    case 16: rc = choose_conv_nt<T, 16>(d, c); break;
+    default: return 0;
+  }
+  return rc == HRP_OK ? c.cfg + (c.t.ksplit > 1 ? 10000 : 0) : 0;
 }
 
 template <typename T>

@@ -406,6 +406,11 @@ int hrp_conv_rowstrip_channels(const hrp_conv_desc* d);
  * 256 input channels and >= 131 072 output pixels - the Bottleneck 1x1 layers at 64 x 64, HRnet.py:60-98), else 0.  Such a
  * problem placed in a HRP_BATCH_CONV launch runs the general tile program: callers launch it on its own.  Host only. */
 int hrp_conv_pointwise(const hrp_conv_desc* d);
+/* CT * 1000 + PT * 100 + WC * 10 + WP - the tile configuration (csrc/conv_tile.h: 32 CT WC output channels x 32 PT WP pixels per
+ * workgroup, WC x WP waves) - when hrp_conv2d_fwd will run problem d on the general tile program, + 10000 when that launch splits K
+ * (two workgroups per output tile, fp32 atomics): 2214, 2114, 1122, 1214 or 1114.  0 when d runs on the row-strip or the pointwise
+ * kernel, is not a valid problem, or fits no configuration.  The answer comes out of the launcher's own candidate walk.  Host only. */
+int hrp_conv_tile_config(const hrp_conv_desc* d);
 int hrp_conv2d_bwd_weight(const hrp_wgrad_desc* d, void* stream);
 /* scratch bytes hrp_conv2d_bwd_weight wants for this problem (0 is never returned for a valid problem) */
 int64_t hrp_wgrad_workspace_bytes(const hrp_wgrad_desc* d);
