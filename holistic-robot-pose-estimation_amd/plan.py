@@ -19,13 +19,11 @@ import os
 import torch
 
 from . import _native as nv
+from . import conv_geometry as G
+from .conv_geometry import rup as _rup
 
 BN_EPS = 1e-5
 STAT_SLOTS = 8   # HRP_STAT_SLOTS in include/hrp.h
-
-
-def _rup(a, b):
-    return (a + b - 1) // b * b
 
 
 def _dt(dtype):
@@ -77,6 +75,10 @@ class TensorH:
 
     def gptr(self):
         return self.grad_buf().data_ptr() + self.offset * self.esz
+
+    def operand(self, grad=False):
+        """This tensor (grad: its gradient buffer) as one side of a convolution / weight-gradient problem."""
+        return G.Operand(self.gptr() if grad else self.ptr(), self.N, self.H, self.W, self.C, self.pitch)
 
     def take_grad_slot(self):
         """-> accumulate flag for a producer of this tensor's gradient."""
@@ -678,7 +680,7 @@ class Plan:
             ws = [w for w in self.weight_list if w.dtype == dtype]
             if not ws:
                 continue
-            esz = 4 if dtype == torch.float32 else 2
+            esz = G.ELEM[_dt(dtype)][0]
             ck = 32 // esz   # channels per 32-byte K chunk (csrc/conv_fwd.hip ROW, core.hip pack kernel)
             total = 0
             for w in ws:
@@ -852,6 +854,13 @@ class Plan:
     def late(self, fn):
         """Defer pointer patching until the arenas exist (finalize)."""
         self._late.append(fn)
+
+    def late_weight(self, w, *descs, transposed=False, field="w"):
+        """Once the arenas exist: the address of w's packed copy (transposed: the data-gradient packing) into `field` of every descriptor."""
+        def patch():
+            for d in descs:
+                setattr(d, field, w.arena.data_ptr() + (w.bwd_off if transposed else w.fwd_off) * G.ELEM[_dt(w.dtype)][0])
+        self.late(patch)
 
     def _table(self, entries):
         tab = (nv.BnEntry * len(entries))()
@@ -1052,9 +1061,6 @@ class Plan:
 # =====================================================================================================
 # Plan builder: the vocabulary modules use in emit()
 # =====================================================================================================
-_TAPS3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
-
-
 class _BwdStack(list):
     """Backward emitters remember the lane they were registered in."""
 
@@ -1146,21 +1152,7 @@ class PlanBuilder(BlockOps, HeadOps):
         assert tuple(weight.shape[2:]) == (7, 7) and xs.C == 4 * cin
         dev, dtype = p.device, xs.dtype
         # index maps (host, once): w' element -> flat index into w (or -1), w element -> flat index into dW'
-        idx_w = torch.full((cout, 4 * cin, 16), -1, dtype=torch.int32)
-        idx_g = torch.zeros((cout, cin, 49), dtype=torch.int32)
-        for dy in range(2):
-            for dx in range(2):
-                for ty in range(4):
-                    for tx in range(4):
-                        ky, kx = 2 * ty + dy - 1, 2 * tx + dx - 1
-                        if ky < 0 or kx < 0:
-                            continue
-                        for c in range(cin):
-                            q = (dy * 2 + dx) * cin + c
-                            for co in range(cout):
-                                idx_w[co, q, ty * 4 + tx] = (co * cin + c) * 49 + ky * 7 + kx
-                                idx_g[co, c, ky * 7 + kx] = (co * 4 * cin + q) * 16 + ty * 4 + tx
-        idx_w, idx_g = idx_w.to(dev), idx_g.to(dev)
+        idx_w, idx_g = (torch.from_numpy(m).to(dev) for m in G.stem_index_maps(cout, cin))
         w12 = torch.zeros(cout, 4 * cin, 4, 4, dtype=torch.float32, device=dev)
         gw12 = torch.zeros(cout, 4 * cin, 16, dtype=torch.float32, device=dev)
         p.keep += [idx_w, idx_g, w12, gw12]
@@ -1173,45 +1165,17 @@ class PlanBuilder(BlockOps, HeadOps):
         p.weight_list.append(w)
         y = p.new(xs.N, xs.H, xs.W, cout, dtype)
         y.requires_grad = p.need_grad
-        taps = [(ty - 2, tx - 2) for ty in range(4) for tx in range(4)]
-        vec = 8 if dtype == torch.bfloat16 else 4
-        d = nv.ConvDesc()
-        d.x, d.y, d.dtype = xs.ptr(), y.ptr(), _cdt(p, dtype)
-        d.N, d.H, d.W, d.Cin, d.x_pitch = xs.N, xs.H, xs.W, _rup(xs.C, vec), xs.pitch
-        d.Ho, d.Wo, d.Cout = y.H, y.W, cout
-        d.y_H, d.y_W, d.y_pitch, d.res_pitch = y.H, y.W, y.pitch, y.pitch
-        d.out_stride, d.in_stride, d.ntaps, d.w_ntaps, d.w_cout_pad = 1, 1, 16, 16, _rup(cout, 32)
-        for i, (a, b) in enumerate(taps):
-            d.dy[i], d.dx[i], d.wtap[i] = a, b, i
+        d = self._conv_desc(G.stem_s2d(xs.H, xs.W), xs.operand(), y.operand(), dtype)
         if want_stats:
             y.stats = p.alloc_stats(cout)
-        esz = 4 if dtype == torch.float32 else 2
-
-        def late():
-            d.w = w.arena.data_ptr() + w.fwd_off * esz
-            if y.stats is not None:
-                d.stats = p.stats.data_ptr() + 8 * y.stats
-        p.late(late)
-        p.fwd.append(Launch("conv", d))
+        self._launch_fwd(d, w, y)
         y.producer = ("conv", d)
         if p.need_grad and weight.requires_grad:
             def bw():
                 if not y.grad_written:
                     return
-                lane = p.cur_lane
-                for grp in range(4):   # weight gradient of the 16 taps in 4 groups of 4 (one kernel row each)
-                    g = nv.WgradDesc()
-                    g.x, g.dy, g.dw, g.dtype = xs.ptr(), y.gptr(), gw12.data_ptr(), _cdt(p, dtype)
-                    g.N, g.H, g.W, g.Cin, g.x_pitch = xs.N, xs.H, xs.W, _rup(xs.C, vec), xs.pitch
-                    g.Ho, g.Wo, g.Cout, g.dy_pitch = y.H, y.W, cout, y.pitch
-                    g.in_stride, g.ntaps = 1, 4
-                    for i in range(4):
-                        g.dy_t[i], g.dx_t[i] = taps[4 * grp + i]
-                    g.dw_cin, g.dw_tap_stride, g.dw_tap_off, g.accumulate = xs.C, 16, 4 * grp, 0
-                    g.reserved = 1    # (plan-side mark: the gather below reads gw12 right away - never a deferred fold)
-                    p.wgrad_ws_bytes[lane] = max(p.wgrad_ws_bytes.get(lane, 0), int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(g))))
-                    p.late(lambda g=g, lane=lane: p.patch_wgrad_ws(g, lane))
-                    p.bwd.append(Launch("wgrad", g))
+                # weight gradient of the 16 taps in 4 groups of 4 (one kernel row each) into gw12, which the gather below reads
+                self._emit_wgrad(G.wgrad_groups(G.TAPS4_STEM, 1), xs.operand(), y.operand(grad=True), w, dtype, scratch=gw12)
                 gp = p.grad_of_param(weight)
                 acc = 1 if p.grad_arena is not None else 0
                 p.bwd.append(lambda s: nv.call("hrp_gather_f32", gw12.data_ptr(), idx_g.data_ptr(), gp.data_ptr(),
@@ -1242,14 +1206,6 @@ class PlanBuilder(BlockOps, HeadOps):
             self.bwd_stack.append(bw)
         return y
 
-    @staticmethod
-    def _class_taps(k, pad, py, px):
-        """Taps of output-parity class (py, px) of a stride-2 transposed convolution / data gradient: the forward conv
-        reads iy = 2 oy + ky - pad, so pixel iy = 2 a + py receives from (ky, oy = a + (py + pad - ky) / 2)."""
-        ys = [(ky, (py + pad - ky) // 2) for ky in range(k) if (py + pad - ky) % 2 == 0]
-        xs = [(kx, (px + pad - kx) // 2) for kx in range(k) if (px + pad - kx) % 2 == 0]
-        return [(oy, ox, ky * k + kx) for (ky, oy) in ys for (kx, ox) in xs]
-
     def deconv4x4s2(self, x, weight, want_stats=False):
         """nn.ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1, bias=False) (full_net.py:194-216).  With V = the
         Conv2d(Cout -> Cin, 4, stride 2, padding 1) whose weight tensor is `weight` itself ([Cin, Cout, 4, 4] = V's
@@ -1260,34 +1216,15 @@ class PlanBuilder(BlockOps, HeadOps):
         cin_t, cout_t = weight.shape[0], weight.shape[1]
         assert tuple(weight.shape[2:]) == (4, 4) and x.C == cin_t
         dtype = x.dtype
-        vec = 8 if dtype == torch.bfloat16 else 4
-        esz = 4 if dtype == torch.float32 else 2
         w = p.weight(weight, cin_t, cout_t, 16)      # as V's weight: cout_V = Cin_T, cin_V = Cout_T
         w.dtype, w.cin_used, w.need_t = dtype, cout_t, True
         y = p.new(x.N, 2 * x.H, 2 * x.W, cout_t, dtype)
         y.requires_grad = p.need_grad
         if want_stats:
             y.stats = p.alloc_stats(cout_t)
-        for (py, px) in [(0, 0), (0, 1), (1, 0), (1, 1)]:
-            d = nv.ConvDesc()
-            d.x, d.y, d.dtype = x.ptr(), y.ptr(), _cdt(p, dtype)
-            d.N, d.H, d.W, d.Cin, d.x_pitch = x.N, x.H, x.W, _rup(x.C, vec), x.pitch
-            d.Cout = cout_t
-            d.y_H, d.y_W, d.y_pitch, d.res_pitch = y.H, y.W, y.pitch, y.pitch
-            d.in_stride, d.out_stride, d.out_off_y, d.out_off_x = 1, 2, py, px
-            d.Ho, d.Wo = (y.H - py + 1) // 2, (y.W - px + 1) // 2
-            tl = self._class_taps(4, 1, py, px)
-            d.ntaps = len(tl)
-            for i, (a, b, t) in enumerate(tl):
-                d.dy[i], d.dx[i], d.wtap[i] = a, b, t
-            d.w_ntaps, d.w_cout_pad = 16, _rup(cout_t, 32)
-
-            def late(d=d):
-                d.w = w.arena.data_ptr() + w.bwd_off * esz
-                if y.stats is not None:
-                    d.stats = p.stats.data_ptr() + 8 * y.stats
-            p.late(late)
-            p.fwd.append(Launch("conv", d))
+        for geo in G.deconv4x4s2_forward(x.H, x.W):
+            d = self._conv_desc(geo, x.operand(), y.operand(), dtype)
+            self._launch_fwd(d, w, y, transposed=True)
         if p.need_grad:
             self.bwd_stack.append(lambda: self._deconv_bwd(x, w, y, dtype))
         return y
@@ -1296,38 +1233,13 @@ class PlanBuilder(BlockOps, HeadOps):
         p = self.plan
         if not y.grad_written:
             return
-        vec = 8 if dtype == torch.bfloat16 else 4
-        esz = 4 if dtype == torch.float32 else 2
-        taps = [(ky - 1, kx - 1) for ky in range(4) for kx in range(4)]
         if w.param.requires_grad:
-            lane = p.cur_lane
-            for grp in range(4):
-                g = nv.WgradDesc()
-                g.x, g.dy, g.dw, g.dtype = y.gptr(), x.ptr(), p.grad_of_param(w.param).data_ptr(), _cdt(p, dtype)
-                g.N, g.H, g.W, g.Cin, g.x_pitch = y.N, y.H, y.W, _rup(y.C, vec), y.pitch
-                g.Ho, g.Wo, g.Cout, g.dy_pitch = x.H, x.W, x.C, x.pitch
-                g.in_stride, g.ntaps = 2, 4
-                for i in range(4):
-                    g.dy_t[i], g.dx_t[i] = taps[4 * grp + i]
-                g.dw_cin, g.dw_tap_stride, g.dw_tap_off = y.C, 16, 4 * grp
-                g.accumulate = 1 if (w.grad_written or p.grad_arena is not None) else 0
-                p.wgrad_ws_bytes[lane] = max(p.wgrad_ws_bytes.get(lane, 0), int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(g))))
-                p.late(lambda g=g, lane=lane: p.patch_wgrad_ws(g, lane))
-                p.bwd.append(Launch("wgrad", g))
-            w.grad_written = True
+            self._emit_wgrad(G.wgrad_groups(G.TAPS4_DECONV, 2), y.operand(grad=True), x.operand(), w, dtype)
         if x.requires_grad:
             acc = x.take_grad_slot()
-            d = nv.ConvDesc()
-            d.x, d.y, d.dtype = y.gptr(), x.gptr(), _cdt(p, dtype)
-            d.N, d.H, d.W, d.Cin, d.x_pitch = y.N, y.H, y.W, _rup(y.C, vec), y.pitch
-            d.Ho, d.Wo, d.Cout = x.H, x.W, x.C
-            d.y_H, d.y_W, d.y_pitch, d.res_pitch = x.H, x.W, x.pitch, x.pitch
-            d.out_stride, d.in_stride, d.ntaps, d.w_ntaps, d.w_cout_pad = 1, 2, 16, 16, _rup(x.C, 32)
-            for i, (a, b) in enumerate(taps):
-                d.dy[i], d.dx[i], d.wtap[i] = a, b, i
-            if acc:
-                d.res = x.gptr()
-            p.late(lambda d=d: setattr(d, "w", w.arena.data_ptr() + w.fwd_off * esz))
+            d = self._conv_desc(G.deconv4x4s2_data_grad(x.H, x.W), y.operand(grad=True), x.operand(grad=True), dtype,
+                                res=(x.gptr(), x.pitch) if acc else None)
+            p.late_weight(w, d)
             p.bwd.append(Launch("conv", d))
 
     def constant(self, N, Cc, value):
@@ -1426,22 +1338,17 @@ class PlanBuilder(BlockOps, HeadOps):
         return v
 
     # ---- convolution ----------------------------------------------------------------------------------
-    def _conv_desc(self, x, w, y, stride, ksize, dtype, into=None, dilation=1):
-        d = into if into is not None else nv.ConvDesc()
-        d.x, d.y = x.ptr(), y.ptr()
-        d.dtype = _cdt(self.plan, dtype)
-        d.N, d.H, d.W, d.Cin, d.x_pitch = x.N, x.H, x.W, _rup(x.C, 8 if dtype == torch.bfloat16 else 4), x.pitch
-        d.Ho, d.Wo, d.Cout = y.H, y.W, y.C
-        d.y_H, d.y_W, d.y_pitch, d.res_pitch = y.H, y.W, y.pitch, y.pitch
-        d.out_stride, d.out_off_y, d.out_off_x = 1, 0, 0
-        d.in_stride = stride
-        taps = _TAPS3 if ksize == 3 else [(0, 0)]
-        d.ntaps = len(taps)
-        for i, (a, b) in enumerate(taps):
-            d.dy[i], d.dx[i], d.wtap[i] = a * dilation, b * dilation, i
-        d.w_ntaps = len(taps)
-        d.w_cout_pad = _rup(y.C, 32)
-        return d
+    def _conv_desc(self, geo, src, dst, dtype, d=None, res=None):
+        """-> the nv.ConvDesc (a new one, or `d`) of geometry `geo` (conv_geometry) from Operand src to Operand dst."""
+        return G.fill_conv(geo, src, dst, _cdt(self.plan, dtype), d=d, res=res)
+
+    def _launch_fwd(self, d, w, y, transposed=False):
+        """The forward launch of d, a producer of y: once the arenas exist its packed weights and, when y has any by then, y's statistics
+        slots are patched in."""
+        p = self.plan
+        p.late_weight(w, d, transposed=transposed)
+        p.late(lambda: y.stats is not None and setattr(d, "stats", p.stats.data_ptr() + 8 * y.stats))
+        p.fwd.append(Launch("conv", d))
 
     def conv(self, x, weight, bias=None, stride=1, want_stats=False, out=None, residual=None, relu=False, dilation=1):
         """y = conv(x) (+bias) (+residual) (ReLU).  weight: torch parameter [Cout, Cin, k, k] or [Cout, Cin].
@@ -1457,29 +1364,19 @@ class PlanBuilder(BlockOps, HeadOps):
         w.dtype = dtype
         w.cin_used = cin
         w.need_t = getattr(w, "need_t", False) or (p.need_grad and x.requires_grad)
-        assert dilation == 1 or (ksize == 3 and stride == 1), "dilated convolutions: 3x3, stride 1"
-        Ho = (x.H + 2 * (ksize // 2) - ksize) // stride + 1
-        Wo = (x.W + 2 * (ksize // 2) - ksize) // stride + 1
-        y = out if out is not None else p.new(x.N, Ho, Wo, cout, dtype)
+        geo = G.forward(x.H, x.W, ksize, stride, dilation)
+        y = out if out is not None else p.new(x.N, geo.Ho, geo.Wo, cout, dtype)
         if dilation > MAX_TILE_DILATION:
             return self._conv_shifted_taps(x, w, y, bias, dilation, dtype, want_stats, residual, relu)
         y.requires_grad = p.need_grad
-        d = self._conv_desc(x, w, y, stride, ksize, dtype, dilation=dilation)
+        d = self._conv_desc(geo, x.operand(), y.operand(), dtype,
+                            res=(residual.ptr(), residual.pitch) if residual is not None else None)
         if bias is not None:
             d.bias = bias.data_ptr()
-        if residual is not None:
-            d.res, d.res_pitch = residual.ptr(), residual.pitch
         d.relu = 1 if relu else 0
         if want_stats:
             y.stats = p.alloc_stats(cout)
-        esz = 4 if dtype == torch.float32 else 2
-
-        def late():
-            d.w = w.arena.data_ptr() + w.fwd_off * esz
-            if y.stats is not None:
-                d.stats = p.stats.data_ptr() + 8 * y.stats
-        p.late(late)
-        p.fwd.append(Launch("conv", d))
+        self._launch_fwd(d, w, y)
         y.producer = ("conv", d)
         if p.need_grad:
             self.bwd_stack.append(lambda: self._conv_bwd(x, w, y, bias, stride, ksize, dtype, residual, relu, dilation))
@@ -1496,61 +1393,42 @@ class PlanBuilder(BlockOps, HeadOps):
         p = self.plan
         if p.need_grad or want_stats or residual is not None or relu:
             raise nv.HrpError(f"conv: dilation {dilation} (beyond the tile halo) is built for inference plans without fused epilogue")
-        esz = 4 if dtype == torch.float32 else 2
-        first = True
-        for i, (a, b) in sorted(enumerate(_TAPS3), key=lambda kv: (kv[1] != (0, 0), kv[0])):
-            dt_y, dt_x = a * dilation, b * dilation
-            y0, y1 = max(0, -dt_y), min(y.H, y.H - dt_y)
-            x0, x1 = max(0, -dt_x), min(y.W, y.W - dt_x)
-            if y1 <= y0 or x1 <= x0:
-                continue
-            d = self._conv_desc(x, w, y, 1, 1, dtype)
-            d.Ho, d.Wo, d.out_off_y, d.out_off_x = y1 - y0, x1 - x0, y0, x0
-            d.ntaps, d.w_ntaps = 1, 9
-            d.dy[0], d.dx[0], d.wtap[0] = y0 + dt_y, x0 + dt_x, i
-            if first:
-                assert (a, b) == (0, 0)
-                if bias is not None:
-                    d.bias = bias.data_ptr()
-            else:
-                d.res, d.res_pitch = y.ptr(), y.pitch
-            first = False
-            p.late(lambda d=d: setattr(d, "w", w.arena.data_ptr() + w.fwd_off * esz))
+        for i, geo in enumerate(G.shifted_taps(y.H, y.W, dilation)):
+            d = self._conv_desc(geo, x.operand(), y.operand(), dtype, res=(y.ptr(), y.pitch) if i else None)
+            if i == 0 and bias is not None:       # (the centre tap, whose rectangle is the whole image)
+                d.bias = bias.data_ptr()
+            p.late_weight(w, d)
             p.fwd.append(Launch("conv", d))
         y.producer = None          # (nothing to fold a BatchNorm into: the sum is complete only after the last launch)
         return y
 
-    def _wgrad_launch(self, x, w, y, ksize=3, stride=1):
-        """Weight-gradient launch of conv(x) -> y for parameter holder w (dW (+)= x^T * y.grad)."""
+    def _emit_wgrad(self, geos, x, dy, w, dtype, scratch=None):
+        """The weight gradient of parameter holder w, dW (+)= x^T * dy (Operands), as the launches `geos` (tap groups of one kernel): per
+        launch the descriptor, the lane's scratch bookkeeping, the late patch of the scratch pointer and the launch itself.  The first
+        gradient of a parameter outside a gradient arena overwrites, every other accumulates.  scratch (the stem): the launches overwrite
+        this fp32 tensor instead, marked reserved = 1 on the plan side - its reader follows right away, never a deferred fold."""
         p = self.plan
-        dtype = x.dtype
-        vec = 8 if dtype == torch.bfloat16 else 4
-        taps = _TAPS3 if ksize == 3 else [(0, 0)]
-        g = nv.WgradDesc()
-        g.x, g.dy, g.dw = x.ptr(), y.gptr(), p.grad_of_param(w.param).data_ptr()
-        g.dtype = _cdt(p, dtype)
-        g.N, g.H, g.W, g.Cin, g.x_pitch = x.N, x.H, x.W, _rup(x.C, vec), x.pitch
-        g.Ho, g.Wo, g.Cout, g.dy_pitch = y.H, y.W, y.C, y.pitch
-        g.in_stride, g.ntaps = stride, len(taps)
-        for i, (a, b) in enumerate(taps):
-            g.dy_t[i], g.dx_t[i] = a, b
-        g.dw_cin = w.cin
-        g.accumulate = 1 if (w.grad_written or p.grad_arena is not None) else 0
-        w.grad_written = True
+        dw = scratch if scratch is not None else p.grad_of_param(w.param)
+        acc = 1 if scratch is None and (w.grad_written or p.grad_arena is not None) else 0
         lane = p.cur_lane
-        p.wgrad_ws_bytes[lane] = max(p.wgrad_ws_bytes.get(lane, 0), int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(g))))
-        p.late(lambda g=g, lane=lane: p.patch_wgrad_ws(g, lane))
-        p.bwd.append(Launch("wgrad", g))
+        for geo in geos:
+            g = G.fill_wgrad(geo, x, dy, dw.data_ptr(), w.cin, _cdt(p, dtype), acc)
+            g.reserved = 0 if scratch is None else 1
+            p.wgrad_ws_bytes[lane] = max(p.wgrad_ws_bytes.get(lane, 0), int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(g))))
+            p.late(lambda g=g: p.patch_wgrad_ws(g, lane))
+            p.bwd.append(Launch("wgrad", g))
+        if scratch is None:
+            w.grad_written = True
 
+    def _wgrad_launch(self, x, w, y, ksize=3, stride=1, dilation=1):
+        """Weight-gradient launch of conv(x) -> y for parameter holder w."""
+        self._emit_wgrad([G.wgrad(ksize, stride, dilation)], x.operand(), y.operand(grad=True), w, x.dtype)
 
     def _conv_bwd(self, x, w, y, bias, stride, ksize, dtype, residual, relu, dilation=1):
         p = self.plan
         assert not relu, "ReLU fused in a conv epilogue is inference-only"
         if not y.grad_written:
             return  # nobody consumed this output
-        esz = 4 if dtype == torch.float32 else 2
-        vec = 8 if dtype == torch.bfloat16 else 4
-        taps = [(a * dilation, b * dilation) for a, b in _TAPS3] if ksize == 3 else [(0, 0)]
         # residual: d_res += dY (fp32 heads only)
         if residual is not None and residual.requires_grad:
             assert dtype == torch.float32
@@ -1573,28 +1451,14 @@ class PlanBuilder(BlockOps, HeadOps):
                                            gb.data_ptr(), 1 if p.grad_arena is not None else 0, cws.data_ptr(), cwb, s))
         # weight gradient
         if w.param.requires_grad:
-            g = nv.WgradDesc()
-            g.x, g.dy, g.dw = x.ptr(), y.gptr(), p.grad_of_param(w.param).data_ptr()
-            g.dtype = _cdt(p, dtype)
-            g.N, g.H, g.W, g.Cin, g.x_pitch = x.N, x.H, x.W, _rup(x.C, vec), x.pitch
-            g.Ho, g.Wo, g.Cout, g.dy_pitch = y.H, y.W, y.C, y.pitch
-            g.in_stride, g.ntaps = stride, len(taps)
-            for i, (a, b) in enumerate(taps):
-                g.dy_t[i], g.dx_t[i] = a, b
-            g.dw_cin = w.cin
-            g.accumulate = 1 if (w.grad_written or p.grad_arena is not None) else 0
-            w.grad_written = True
-            lane = p.cur_lane
-            p.wgrad_ws_bytes[lane] = max(p.wgrad_ws_bytes.get(lane, 0), int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(g))))
-            p.late(lambda g=g, lane=lane: p.patch_wgrad_ws(g, lane))
-            p.bwd.append(Launch("wgrad", g))
+            self._wgrad_launch(x, w, y, ksize, stride, dilation)
         # data gradient
         if x.requires_grad:
             acc = x.take_grad_slot()
-            classes = [(0, 0)] if stride == 1 else [(0, 0), (0, 1), (1, 0), (1, 1)]
+            assert stride in (1, 2)
             if stride == 2 and ksize == 1 and not acc:
                 # only the even pixels are written below: clear the buffer, then accumulate into it
-                gb_bytes = x.N * x.H * x.W * x.pitch * esz
+                gb_bytes = x.N * x.H * x.W * x.pitch * G.ELEM[_dt(dtype)][0]
                 p.bwd.append(lambda s: nv.call("hrp_fill_zero", x.gptr(), gb_bytes, s))
                 acc = 1
             # stride-2 3x3 layers below ~4 GFLOP of data gradient (the fuse / transition layers of the branches: launch-latency
@@ -1604,49 +1468,17 @@ class PlanBuilder(BlockOps, HeadOps):
                     2.0 * 9 * y.N * y.H * y.W * y.C * x.C < 4e9)
             if pad4:
                 w.pad_t = 1
-            par = None
-            if len(classes) > 1:   # the parity classes write disjoint pixels: virtual lanes, one batched launch per tap count
-                vp = self.parallel(len(classes), virtual=True)
-                par = vp.__enter__()
-            for ci, (py, px) in enumerate(classes):
-                d = nv.ConvDesc()
-                d.x, d.y = y.gptr(), x.gptr()
-                d.dtype = _cdt(p, dtype)
-                d.N, d.H, d.W, d.Cin, d.x_pitch = y.N, y.H, y.W, _rup(y.C, vec), y.pitch
-                d.Cout = x.C
-                d.y_H, d.y_W, d.y_pitch = x.H, x.W, x.pitch
-                d.in_stride = 1
-                if stride == 1:
-                    d.Ho, d.Wo = x.H, x.W
-                    d.out_stride, d.out_off_y, d.out_off_x = 1, 0, 0
-                    tl = [(-a, -b, i) for i, (a, b) in enumerate(taps)]
-                else:
-                    assert ksize in (1, 3) and stride == 2
-                    d.Ho, d.Wo = (x.H - py + 1) // 2, (x.W - px + 1) // 2
-                    d.out_stride, d.out_off_y, d.out_off_x = 2, py, px
-                    # forward: iy = 2*oy + ky - pad  ->  pixel 2a+py receives from (ky, oy = a + (py + pad - ky) / 2)
-                    tl = self._class_taps(ksize, ksize // 2, py, px)
-                    if not tl:       # 1x1 stride 2: the odd pixels get no gradient from this conv
-                        continue
-                if pad4:
-                    tl = tl + [(tl[0][0], tl[0][1], len(taps))] * (4 - len(tl))      # (zero slot; any offset inside the halo)
-                d.ntaps = len(tl)
-                for i, (a, b, t) in enumerate(tl):
-                    d.dy[i], d.dx[i], d.wtap[i] = a, b, t
-                d.w_ntaps = len(taps) + (1 if pad4 else 0)
-                w.t_ntaps.add(int(d.w_ntaps))
-                d.w_cout_pad = _rup(x.C, 32)
-                p.late(lambda d=d: setattr(d, "w", w.arena.data_ptr() + w.bwd_off * esz))
-                if acc:
-                    d.res, d.res_pitch = x.gptr(), x.pitch
-                if d.Ho > 0 and d.Wo > 0:
-                    if par is not None:
-                        with par.lane(ci):
-                            p.bwd.append(Launch("conv", d))
-                    else:
+            w.t_ntaps.add(ksize * ksize + (1 if pad4 else 0))
+            geos = [G.data_grad_s1(x.H, x.W, ksize, dilation)] if stride == 1 else G.data_grad_s2(x.H, x.W, ksize, pad4)
+            # (without a residual res_pitch stays 0 here, unlike in the forward descriptors)
+            res = (x.gptr(), x.pitch) if acc else (None, 0)
+            # stride 2: the parity classes write disjoint pixels: virtual lanes (the class index), one batched launch per tap count
+            with self.parallel(4, virtual=True) if stride == 2 else contextlib.nullcontext() as par:
+                for geo in geos:
+                    d = self._conv_desc(geo, y.operand(grad=True), x.operand(grad=True), dtype, res=res)
+                    p.late_weight(w, d, transposed=True)
+                    with par.lane(geo.cls) if par else contextlib.nullcontext():
                         p.bwd.append(Launch("conv", d))
-            if par is not None:
-                vp.__exit__(None, None, None)
 
     # ---- element-wise ---------------------------------------------------------------------------------
     def _fold(self, bn):

@@ -7,11 +7,11 @@ bottleneck_tail     conv3 (+ projection) + BN + shortcut + ReLU of a wide Bottle
 
 The switches (ROWCONV_FUSE, BLOCK_END_*, BNECK_TAIL_FUSE ..) live in the plan module, where tests and tools patch them."""
 import ctypes as C
-import math
 
 import torch
 
 from . import _native as nv
+from . import conv_geometry as G
 from . import plan as PL
 
 
@@ -34,22 +34,20 @@ class BlockOps:
         w1, w2 = p.weight(conv1_w, Cc, Cc, 9), p.weight(conv2_w, Cc, Cc, 9)
         out = p.new(x.N, x.H, x.W, Cc, dtype)
         b = nv.BlockDesc()
-        d1 = self._conv_desc(x, w1, out, 1, 3, dtype, into=b.conv1)
-        d2 = self._conv_desc(x, w2, out, 1, 3, dtype, into=b.conv2)
+        geo, mid = G.forward(x.H, x.W, 3), out.operand()._replace(ptr=None)     # (the intermediate stays in LDS)
+        d1 = self._conv_desc(geo, x.operand(), mid, dtype, d=b.conv1)
+        d2 = self._conv_desc(geo, mid, out.operand(), dtype, d=b.conv2, res=(x.ptr(), x.pitch))
         (sc1, sh1), (sc2, sh2) = self._fold(bn1), self._fold(bn2)
-        d1.scale, d1.shift, d1.relu, d1.y = sc1.data_ptr(), sh1.data_ptr(), 1, None
-        d2.scale, d2.shift, d2.relu, d2.x = sc2.data_ptr(), sh2.data_ptr(), 1, None
-        d2.res, d2.res_pitch = x.ptr(), x.pitch
-        d1.w = d2.w = x.ptr()                      # (placeholders for the host-side shape query; final in late())
+        d1.scale, d1.shift, d1.relu = sc1.data_ptr(), sh1.data_ptr(), 1
+        d2.scale, d2.shift, d2.relu = sc2.data_ptr(), sh2.data_ptr(), 1
+        d1.w = d2.w = x.ptr()                      # (placeholders for the host-side shape query; final at finalize)
         if nv.lib().hrp_block_channels(C.byref(b)) != Cc:
             return None
         for w in (w1, w2):
             w.dtype, w.cin_used = dtype, Cc
             w.need_t = getattr(w, "need_t", False)
-
-        def late():
-            d1.w, d2.w = w1.arena.data_ptr() + w1.fwd_off * 2, w2.arena.data_ptr() + w2.fwd_off * 2
-        p.late(late)
+        p.late_weight(w1, d1)
+        p.late_weight(w2, d2)
         p.fwd.append(PL.BlockLaunch(b))
         out.producer = None
         p.counters["block_fused"] = p.counters.get("block_fused", 0) + 1
@@ -89,7 +87,8 @@ class BlockOps:
         x.check_readable()
         dtype = x.dtype
         w1 = p.weight(conv1_w, Cc, Cc, 9)
-        probe = self._conv_desc(x, w1, x, 1, 3, dtype)       # geometry only; dummy aligned pointers
+        geo = G.forward(x.H, x.W, 3)
+        probe = self._conv_desc(geo, x.operand(), x.operand(), dtype)       # geometry only; dummy aligned pointers
         probe.w = probe.x
         probe.pro_mode, probe.pro_stats, probe.pro_gamma, probe.pro_beta = 1, probe.x, probe.x, probe.x
         if nv.lib().hrp_conv_rowstrip_channels(C.byref(probe)) != Cc:
@@ -102,7 +101,6 @@ class BlockOps:
         for w in (w1, w2):
             w.dtype, w.cin_used = dtype, Cc
             w.need_t = getattr(w, "need_t", False) or p.need_grad
-        esz = 2
         cnt = float(x.N * x.H * x.W)
         y1, h, y2 = p.new(x.N, x.H, x.W, Cc, dtype), p.new(x.N, x.H, x.W, Cc, dtype), p.new(x.N, x.H, x.W, Cc, dtype)
         for t in (y1, h, y2):
@@ -110,20 +108,22 @@ class BlockOps:
         y1.stats, y2.stats = p.alloc_stats(Cc), p.alloc_stats(Cc)
         p.bn_train.append((bn1, y1.stats, x.N * x.H * x.W))
         gam, bet = bn1.weight.data_ptr(), bn1.bias.data_ptr()
-        d1 = self._conv_desc(x, w1, y1, 1, 3, dtype)
-        d2 = self._conv_desc(y1, w2, y2, 1, 3, dtype)
+        d1 = self._conv_desc(geo, (x if pend is None else pend["y2"]).operand(), y1.operand(), dtype)
+        d2 = self._conv_desc(geo, y1.operand(), y2.operand(), dtype)
         d2.pro_mode, d2.pro_gamma, d2.pro_beta, d2.pro_count, d2.pro_eps, d2.pro_side = 1, gam, bet, cnt, bn1.eps, h.ptr()
         if pend is not None:
             # conv1 stages the previous block's raw conv2 output and turns it into x = relu(bn2'(y2') + x') in place; x and its
             # ReLU bits (what the previous block's backward reads) leave as side outputs
             py2, px, pbn = pend["y2"], pend["x"], pend["bn"]
-            d1.x, d1.pro_mode, d1.pro_x2 = py2.ptr(), 3, px.ptr()
+            assert (py2.N, py2.H, py2.W, py2.C, py2.pitch) == (x.N, x.H, x.W, x.C, x.pitch)
+            d1.pro_mode, d1.pro_x2 = 3, px.ptr()
             d1.pro_gamma, d1.pro_beta, d1.pro_count, d1.pro_eps = pbn.weight.data_ptr(), pbn.bias.data_ptr(), cnt, pbn.eps
             d1.pro_side, d1.pro_mask = x.ptr(), pend["mask"]
             p.counters["block_end_forward_fused"] = p.counters.get("block_end_forward_fused", 0) + 1
+        p.late_weight(w1, d1)
+        p.late_weight(w2, d2)
 
         def late():
-            d1.w, d2.w = w1.arena.data_ptr() + w1.fwd_off * esz, w2.arena.data_ptr() + w2.fwd_off * esz
             d1.stats, d2.stats = p.stats.data_ptr() + 8 * y1.stats, p.stats.data_ptr() + 8 * y2.stats
             d2.pro_stats = d1.stats
             if pend is not None:
@@ -167,15 +167,14 @@ class BlockOps:
                 h.take_grad_slot()
                 boff = p.alloc_bsums(Cc)
                 p.bn_bwd.append((bn1, boff))
-                g2 = nv.ConvDesc()
-                self._conv_desc(y2, w2, h, 1, 3, dtype, into=g2)
-                g2.x, g2.y = y2.gptr() if (fd is None) else 0, h.gptr()
+                # (with the block end fused its gradient out.grad is the staged operand: same shape as y2)
+                bgeo = G.data_grad_s1(x.H, x.W, 3)
+                g2 = self._conv_desc(bgeo, (y2 if fd is None else out).operand(grad=True), h.operand(grad=True), dtype)
                 red = None
                 if fd is not None:
                     # the block-end BatchNorm + ReLU backward (bn2, mask bits): staged operand of this launch
                     boff2 = p.alloc_bsums(Cc)
                     p.bn_bwd.append((bn2, boff2))
-                    g2.x = out.gptr()
                     g2.pro_mode, g2.pro_x2, g2.pro_gamma, g2.pro_beta = 2, y2.ptr(), bn2.weight.data_ptr(), bn2.bias.data_ptr()
                     g2.pro_count, g2.pro_eps, g2.pro_mask = cnt, bn2.eps, fd.mask
                     g2.pro_side = y2.gptr()
@@ -201,18 +200,12 @@ class BlockOps:
                         red = b
                         p.bwd.append(PL.Launch("ew_red", b))
                     p.counters["block_end_apply_fused"] = p.counters.get("block_end_apply_fused", 0) + 1
-                for i, (a, b) in enumerate(PL._TAPS3):
-                    g2.dy[i], g2.dx[i], g2.wtap[i] = -a, -b, i
                 g2.bnb_x, g2.bnb_x_pitch = y1.ptr(), y1.pitch
                 g2.bnb_gamma, g2.bnb_beta, g2.bnb_count, g2.bnb_eps = gam, bet, cnt, bn1.eps
                 # data gradient of conv1 -> x.grad; its staged operand is the BatchNorm + ReLU backward of (h.grad, y1)
                 y1.take_grad_slot()
                 acc = x.take_grad_slot()
-                g1 = nv.ConvDesc()
-                self._conv_desc(h, w1, x, 1, 3, dtype, into=g1)
-                g1.x, g1.y = h.gptr(), x.gptr()
-                for i, (a, b) in enumerate(PL._TAPS3):
-                    g1.dy[i], g1.dx[i], g1.wtap[i] = -a, -b, i
+                g1 = self._conv_desc(bgeo, h.operand(grad=True), x.operand(grad=True), dtype)
                 if fd is not None and masked_res:
                     assert not acc
                     g1.res, g1.res_pitch, g1.res_mask = out.gptr(), out.pitch, fd.mask
@@ -221,9 +214,10 @@ class BlockOps:
                     g1.res, g1.res_pitch = x.gptr(), x.pitch
                 g1.pro_mode, g1.pro_x2, g1.pro_gamma, g1.pro_beta, g1.pro_count, g1.pro_eps = 2, y1.ptr(), gam, bet, cnt, bn1.eps
                 g1.pro_side = y1.gptr()
+                p.late_weight(w2, g2, transposed=True)
+                p.late_weight(w1, g1, transposed=True)
 
                 def late_b():
-                    g2.w, g1.w = w2.arena.data_ptr() + w2.bwd_off * esz, w1.arena.data_ptr() + w1.bwd_off * esz
                     g2.stats = p.bsums.data_ptr() + 8 * boff
                     g2.bnb_stats = g1.pro_stats = p.stats.data_ptr() + 8 * y1.stats
                     g1.pro_bsums = g2.stats
@@ -294,7 +288,7 @@ class BlockOps:
 
         def desc(mode, second=False):
             src, w, y, bn = (x, wd, yd, proj[1]) if second else (h, w3, y3, bn3)
-            d = self._conv_desc(src, w, y, 1, 1, dtype)
+            d = self._conv_desc(G.forward(src.H, src.W, 1), src.operand(), y.operand(), dtype)
             d.tail_mode = mode
             d.tail_gamma, d.tail_beta, d.tail_count, d.tail_eps = bn.weight.data_ptr(), bn.bias.data_ptr(), cnt, bn.eps
             d.tail_mask = mask.data_ptr()
@@ -327,12 +321,14 @@ class BlockOps:
             yd.requires_grad = p.need_grad
             yd.stats = p.alloc_stats(cout)
             p.bn_train.append((proj[1], yd.stats, h.N * h.H * h.W))
+        p.late_weight(w3, dA, dB)
+        if proj is not None:
+            p.late_weight(wd, dA2)
+            p.late_weight(wd, dB, field="tail_w2")
 
         def late():
-            dA.w = dB.w = w3.arena.data_ptr() + w3.fwd_off * 2
             dA.stats = dB.tail_stats = p.stats.data_ptr() + 8 * y3.stats
             if proj is not None:
-                dA2.w = dB.tail_w2 = wd.arena.data_ptr() + wd.fwd_off * 2
                 dA2.stats = dB.tail_stats2 = p.stats.data_ptr() + 8 * yd.stats
         p.late(late)
         p.fwd.append(PL.Launch("conv", dA))
@@ -356,11 +352,12 @@ class BlockOps:
                     if proj is None:
                         dD.tail_side, dD.tail_side_acc = x.gptr(), x.take_grad_slot()
 
-                    def late_b(dC=dC, dD=dD, w=w, y=y, boff=boff):
-                        dC.w = dD.w = w.arena.data_ptr() + w.fwd_off * 2
+
+                    def late_b(dC=dC, dD=dD, y=y, boff=boff):
                         dC.tail_stats = dD.tail_stats = p.stats.data_ptr() + 8 * y.stats
                         dC.stats = dD.tail_bsums = p.bsums.data_ptr() + 8 * boff
                     p.late(late_b)
+                    p.late_weight(w, dC, dD)
                     p.bwd.append(PL.Launch("conv", dC))
                     p.bwd.append(PL.Launch("conv", dD))
                 self._conv_bwd(h, w3, y3, None, 1, 1, dtype, None, False)

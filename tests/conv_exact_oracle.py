@@ -3,8 +3,9 @@
     y[n, oy * out_stride + out_off_y, ox * out_stride + out_off_x, :] = epilogue( sum_i W[wtap[i]] . x[n, oy * in_stride + dy[i], ox * in_stride + dx[i], :] )
 
 with zero outside the image and the epilogue  v + bias -> v * scale + shift -> v + res -> relu(v).  Nothing here knows how a kernel
-tiles, stages or orders the sum.  Also here: the descriptors the plans build (plan.py::_conv_desc / _conv_bwd / stem7x7_s2d) restated
-as tap lists, and the integer operand generators of the exact-arithmetic tests.
+tiles, stages or orders the sum, nor which taps and windows the plans choose: those come from the package's conv_geometry module
+(from_geometry) or from a descriptor the real builder filled (problem_of).  Also here: the same literal evaluation of an hrp_wgrad_desc,
+and the integer operand generators of the exact-arithmetic tests.
 
 With small non-zero integer operands every product and every partial sum of a problem is an integer below 2^24: bf16 MFMA, fp32 and
 the fp32x3 split all compute it exactly in any order, the oracle is exact, and a kernel is compared with torch.equal.  A bf16 output
@@ -15,7 +16,6 @@ from typing import List, Optional, Tuple
 import torch
 
 F64 = torch.float64
-TAPS3 = [(ky - 1, kx - 1) for ky in range(3) for kx in range(3)]
 
 
 @dataclass
@@ -114,46 +114,7 @@ def evaluate(p: Problem, y0: Optional[torch.Tensor] = None, acc: Optional[torch.
     return Result(y, written(p), pre, v, torch.cat([v.sum((0, 1, 2)), (v * v).sum((0, 1, 2))]))
 
 
-# ---- the descriptors the plans build, as tap lists ------------------------------------------------------------------------------
-
-def forward_taps(ksize, dilation=1):
-    """plan.py::_conv_desc: 3x3 (padding = dilation) or 1x1, tap i reads slot i."""
-    taps = TAPS3 if ksize == 3 else [(0, 0)]
-    return [(a * dilation, b * dilation, i) for i, (a, b) in enumerate(taps)]
-
-
-def mirrored_taps(ksize, dilation=1):
-    """plan.py::_conv_bwd, stride 1: the data gradient is the same sum with mirrored offsets on the transposed packing."""
-    return [(-a, -b, i) for a, b, i in forward_taps(ksize, dilation)]
-
-
-def class_taps(k, pad, py, px):
-    """plan.py::_class_taps: taps of output-parity class (py, px) of a stride-2 data gradient.  The forward conv reads
-    iy = 2 oy + ky - pad, so pixel iy = 2 a + py receives from (ky, oy = a + (py + pad - ky) / 2)."""
-    ys = [(ky, (py + pad - ky) // 2) for ky in range(k) if (py + pad - ky) % 2 == 0]
-    xs = [(kx, (px + pad - kx) // 2) for kx in range(k) if (px + pad - kx) % 2 == 0]
-    return [(oy, ox, ky * k + kx) for (ky, oy) in ys for (kx, ox) in xs]
-
-
-def stem_taps():
-    """plan.py::stem7x7_s2d: the 7x7 stride-2 stem as a 4x4 stride-1 convolution over the 2x2 space-to-depth image."""
-    return [(ty - 2, tx - 2, ty * 4 + tx) for ty in range(4) for tx in range(4)]
-
-
-def stem_weight_s2d(w7):
-    """[Cout, C, 7, 7] -> [Cout, 4 C, 16]: w'[co][(dy, dx, c)][ty, tx] = w[co][c][2 ty + dy - 1][2 tx + dx - 1], zero where the 8x8
-    embedding has no 7x7 entry."""
-    cout, cin = w7.shape[:2]
-    out = torch.zeros(cout, 4 * cin, 16, dtype=w7.dtype)
-    for dy in range(2):
-        for dx in range(2):
-            for ty in range(4):
-                for tx in range(4):
-                    ky, kx = 2 * ty + dy - 1, 2 * tx + dx - 1
-                    if ky >= 0 and kx >= 0:
-                        out[:, (dy * 2 + dx) * cin:(dy * 2 + dx + 1) * cin, ty * 4 + tx] = w7[:, :, ky, kx]
-    return out
-
+# ---- operands and packings ----------------------------------------------------------------------------------------------------------
 
 def space_to_depth(x_nchw):
     """hrp_nchw_to_nhwc_s2d: dst[n, y, x, (dy * 2 + dx) * C + c] = src[n, c, 2 y + dy, 2 x + dx]."""
@@ -173,6 +134,57 @@ def slots_bwd(w, pad_t=0):
     if pad_t:
         s = torch.cat([s, torch.zeros(pad_t, *s.shape[1:], dtype=s.dtype)], 0)
     return s
+
+
+# ---- geometries and descriptors read back ---------------------------------------------------------------------------------------------------------
+
+def from_geometry(x, w, geo, y_H=0, y_W=0, y_pitch=0, **kw):
+    """A conv_geometry.ConvGeometry (window, strides, taps) on the operands x and w as a Problem."""
+    assert w.shape[0] == geo.w_ntaps, "the geometry reads another packing"
+    return Problem(x, w, list(geo.taps), geo.Ho, geo.Wo, y_H=y_H, y_W=y_W, y_pitch=y_pitch, in_stride=geo.in_stride,
+                   out_stride=geo.out_stride, out_off=(geo.out_off_y, geo.out_off_x), **kw)
+
+
+def problem_of(d, x, slots, res=None, bias=None, scale=None, shift=None):
+    """A filled hrp_conv_desc (ctypes nv.ConvDesc) as a Problem on the host operands x [N, H, W, C] and slots [w_ntaps, Cout, C]:
+    window, strides and taps are the descriptor's; the descriptor must describe these operands (shapes, tap slots, channel padding)."""
+    N, H, W, Cc = x.shape
+    assert (d.N, d.H, d.W) == (N, H, W) and Cc <= d.Cin <= d.x_pitch, "the descriptor reads another input"
+    assert tuple(slots.shape) == (d.w_ntaps, d.Cout, Cc) and d.w_cout_pad == -(-d.Cout // 32) * 32, "the descriptor reads another packing"
+    assert 0 < d.ntaps <= len(d.dy) and d.Cout <= d.y_pitch
+    taps = [(d.dy[i], d.dx[i], d.wtap[i]) for i in range(d.ntaps)]
+    assert all(0 <= t < d.w_ntaps for _, _, t in taps), "a tap reads a slot the packing does not have"
+    return Problem(x, slots, taps, d.Ho, d.Wo, y_H=d.y_H, y_W=d.y_W, y_pitch=d.y_pitch, in_stride=d.in_stride, out_stride=d.out_stride,
+                   out_off=(d.out_off_y, d.out_off_x), bias=bias, scale=scale, shift=shift, res=res, relu=bool(d.relu))
+
+
+def evaluate_wgrad(g, x, dy, dw0=None):
+    """hrp_wgrad_desc (include/hrp.h) evaluated literally in float64 on x [N, H, W, Cin] and dy [N, Ho, Wo, Cout]:
+
+        dW[co][ci][t] (+)= sum_{n, oy, ox} dy[n, oy, ox, co] * x[n, oy * in_stride + dy_t[t], ox * in_stride + dx_t[t], ci]
+
+    stored at (co * dw_cin + ci) * T + dw_tap_off + t with T = dw_tap_stride or, 0, ntaps.  -> (dw [Cout, dw_cin, T] after the launch
+    given its contents before (dw0, zero when None), bool mask of the elements the launch writes)."""
+    N, H, W, Cc = x.shape
+    assert (g.N, g.H, g.W) == (N, H, W) and Cc <= g.Cin <= g.x_pitch and Cc <= g.dw_cin, "the descriptor reads another input"
+    assert tuple(dy.shape) == (N, g.Ho, g.Wo, g.Cout) and g.Cout <= g.dy_pitch, "the descriptor reads another output gradient"
+    T = g.dw_tap_stride or g.ntaps
+    assert 0 < g.ntaps and 0 <= g.dw_tap_off and g.dw_tap_off + g.ntaps <= T
+    dw = torch.zeros(g.Cout, g.dw_cin, T, dtype=F64) if dw0 is None else dw0.to(F64).clone()
+    assert tuple(dw.shape) == (g.Cout, g.dw_cin, T)
+    wr = torch.zeros_like(dw, dtype=torch.bool)
+    x, dy, s = x.to(F64), dy.to(F64), g.in_stride
+    for t in range(g.ntaps):
+        a0, a1 = _span(g.Ho, H, s, g.dy_t[t])
+        b0, b1 = _span(g.Wo, W, s, g.dx_t[t])
+        v = torch.zeros(g.Cout, Cc, dtype=F64)
+        if a1 > a0 and b1 > b0:
+            xs = x[:, a0 * s + g.dy_t[t]:(a1 - 1) * s + g.dy_t[t] + 1:s, b0 * s + g.dx_t[t]:(b1 - 1) * s + g.dx_t[t] + 1:s, :]
+            v = torch.einsum("nyxo,nyxc->oc", dy[:, a0:a1, b0:b1], xs)
+        k = g.dw_tap_off + t
+        dw[:, :Cc, k] = v + (dw[:, :Cc, k] if g.accumulate else 0)
+        wr[:, :Cc, k] = True
+    return dw, wr
 
 
 # ---- integer operands -----------------------------------------------------------------------------------------------------------

@@ -1,12 +1,16 @@
-"""The float64 convolution oracle of the exact-arithmetic tests (tests/conv_exact_oracle.py) proved against torch's own convolutions in
-double on the CPU - no GPU, no call into the library - for every descriptor form the plans build, and the integer operand generators
-checked for the preconditions the GPU tests (test_gpu_conv_exact.py) assert before a launch."""
+"""The float64 convolution oracle of the exact-arithmetic tests (tests/conv_exact_oracle.py) and the geometries the plans build from
+(the package's conv_geometry module: taps, windows, parity classes, the stem's index maps) proved together against torch's own
+convolutions in double on the CPU - no GPU - for every descriptor form, and the integer operand generators checked for the
+preconditions the GPU tests (test_gpu_conv_exact.py) assert before a launch."""
 import pytest
 import torch
 import torch.nn.functional as F
 
 import conv_exact_oracle as O
 from conv_exact_oracle import F64
+
+import hrpe_amd  # noqa: F401
+from hrpe_amd import conv_geometry as G
 
 
 def nchw(t):
@@ -24,7 +28,9 @@ def test_oracle_3x3_forward(stride, hw):
     H, W = hw
     x, w = rnd(g, 2, H, W, 5), rnd(g, 6, 5, 9)
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    r = O.evaluate(O.Problem(x, O.slots_fwd(w), O.forward_taps(3), Ho, Wo, in_stride=stride))
+    geo = G.forward(H, W, 3, stride)
+    assert (geo.Ho, geo.Wo) == (Ho, Wo)
+    r = O.evaluate(O.from_geometry(x, O.slots_fwd(w), geo))
     ref = F.conv2d(nchw(x), w.view(6, 5, 3, 3), stride=stride, padding=1)
     assert torch.allclose(nchw(r.y), ref, rtol=0, atol=1e-12)
     assert bool(r.written.all())
@@ -33,9 +39,9 @@ def test_oracle_3x3_forward(stride, hw):
 def test_oracle_1x1_stride2_and_dilation2():
     g = torch.Generator().manual_seed(2)
     x, w1, w3 = rnd(g, 2, 9, 12, 4), rnd(g, 3, 4, 1), rnd(g, 3, 4, 9)
-    r = O.evaluate(O.Problem(x, O.slots_fwd(w1), O.forward_taps(1), 5, 6, in_stride=2))
+    r = O.evaluate(O.from_geometry(x, O.slots_fwd(w1), G.forward(9, 12, 1, 2)))
     assert torch.allclose(nchw(r.y), F.conv2d(nchw(x), w1.view(3, 4, 1, 1), stride=2), rtol=0, atol=1e-12)
-    r = O.evaluate(O.Problem(x, O.slots_fwd(w3), O.forward_taps(3, 2), 9, 12))
+    r = O.evaluate(O.from_geometry(x, O.slots_fwd(w3), G.forward(9, 12, 3, 1, 2)))
     assert torch.allclose(nchw(r.y), F.conv2d(nchw(x), w3.view(3, 4, 3, 3), padding=2, dilation=2), rtol=0, atol=1e-12)
 
 
@@ -43,7 +49,7 @@ def test_oracle_1x1_stride2_and_dilation2():
 def test_oracle_stride1_data_gradient_is_the_mirrored_problem(dilation):
     g = torch.Generator().manual_seed(3)
     dy, w = rnd(g, 2, 7, 6, 4), rnd(g, 4, 5, 9)          # layer 5 -> 4
-    r = O.evaluate(O.Problem(dy, O.slots_bwd(w), O.mirrored_taps(3, dilation), 7, 6))
+    r = O.evaluate(O.from_geometry(dy, O.slots_bwd(w), G.data_grad_s1(7, 6, 3, dilation)))
     ref = F.conv_transpose2d(nchw(dy), w.view(4, 5, 3, 3), padding=dilation, dilation=dilation)
     assert torch.allclose(nchw(r.y), ref, rtol=0, atol=1e-12)
 
@@ -60,17 +66,17 @@ def test_oracle_stride2_data_gradient_by_parity_classes(hw, padded):
     slots = O.slots_bwd(w, pad_t=1 if padded else 0)
     buf = torch.full((2, H, W, 3), 7.0, dtype=F64)
     seen = torch.zeros(2, H, W, 3, dtype=torch.int32)
-    counts = []
-    for py in range(2):
-        for px in range(2):
-            tl = O.class_taps(3, 1, py, px)
-            counts.append(len(tl))
-            if padded:
-                tl = tl + [(tl[0][0], tl[0][1], 9)] * (4 - len(tl))
-            r = O.evaluate(O.Problem(dy, slots, tl, (H - py + 1) // 2, (W - px + 1) // 2, y_H=H, y_W=W, out_stride=2, out_off=(py, px)), y0=buf)
-            assert torch.equal(r.y[~r.written], buf[~r.written])
-            buf, seen = r.y, seen + r.written.int()
-    assert sorted(counts) == [1, 2, 2, 4]
+    geos = G.data_grad_s2(H, W, 3, pad4=padded)
+    assert [(q.cls, q.out_off_y, q.out_off_x, q.out_stride) for q in geos] == [(0, 0, 0, 2), (1, 0, 1, 2), (2, 1, 0, 2), (3, 1, 1, 2)]
+    for q in geos:
+        # a padding tap repeats the class's first offset and reads the zero slot 9
+        real = [t for t in q.taps if t[2] < 9]
+        assert real == G.class_taps(3, 1, q.out_off_y, q.out_off_x)
+        assert q.taps[len(real):] == ([(real[0][0], real[0][1], 9)] * (4 - len(real)) if padded else [])
+        r = O.evaluate(O.from_geometry(dy, slots, q, y_H=H, y_W=W), y0=buf)
+        assert torch.equal(r.y[~r.written], buf[~r.written])
+        buf, seen = r.y, seen + r.written.int()
+    assert sorted(len([t for t in q.taps if t[2] < 9]) for q in geos) == [1, 2, 2, 4]
     assert bool((seen == 1).all())
     ref = F.conv_transpose2d(nchw(dy), w.view(4, 3, 3, 3), stride=2, padding=1, output_padding=(H - 1 - 2 * (Ho - 1), W - 1 - 2 * (Wo - 1)))
     assert torch.allclose(nchw(buf), ref, rtol=0, atol=1e-12)
@@ -79,8 +85,10 @@ def test_oracle_stride2_data_gradient_by_parity_classes(hw, padded):
 def test_oracle_1x1_stride2_data_gradient_accumulates_on_even_pixels():
     g = torch.Generator().manual_seed(5)
     dy, w, prev = rnd(g, 2, 4, 5, 6), rnd(g, 6, 3, 1), rnd(g, 2, 8, 9, 3)
-    assert [len(O.class_taps(1, 0, py, px)) for py in range(2) for px in range(2)] == [1, 0, 0, 0]
-    r = O.evaluate(O.Problem(dy, O.slots_bwd(w), O.class_taps(1, 0, 0, 0), 4, 5, y_H=8, y_W=9, out_stride=2, res=prev), y0=prev)
+    assert [len(G.class_taps(1, 0, py, px)) for py in range(2) for px in range(2)] == [1, 0, 0, 0]
+    (geo,) = G.data_grad_s2(8, 9, 1)             # the three classes without a tap are no problem
+    assert geo.cls == 0
+    r = O.evaluate(O.from_geometry(dy, O.slots_bwd(w), geo, y_H=8, y_W=9, res=prev), y0=prev)
     ref = prev + F.conv_transpose2d(nchw(dy), w.view(6, 3, 1, 1), stride=2, output_padding=(1, 0)).permute(0, 2, 3, 1)
     assert torch.allclose(r.y, ref, rtol=0, atol=1e-12)
     assert int(r.written.sum()) == 2 * 4 * 5 * 3
@@ -89,8 +97,11 @@ def test_oracle_1x1_stride2_data_gradient_accumulates_on_even_pixels():
 def test_oracle_space_to_depth_stem():
     g = torch.Generator().manual_seed(6)
     img, w7 = rnd(g, 2, 3, 16, 12), rnd(g, 5, 3, 7, 7)
-    r = O.evaluate(O.Problem(O.space_to_depth(img), O.slots_fwd(O.stem_weight_s2d(w7)), O.stem_taps(), 8, 6))
+    idx_w, idx_g = (torch.from_numpy(m).long() for m in G.stem_index_maps(5, 3))
+    w12 = torch.where(idx_w >= 0, w7.reshape(-1)[idx_w.clamp_min(0)], torch.zeros((), dtype=F64))      # (hrp_gather_f32)
+    r = O.evaluate(O.from_geometry(O.space_to_depth(img), O.slots_fwd(w12), G.stem_s2d(8, 6)))
     assert torch.allclose(nchw(r.y), F.conv2d(img, w7, stride=2, padding=3), rtol=0, atol=1e-12)
+    assert torch.equal(idx_w.reshape(-1)[idx_g], torch.arange(5 * 3 * 49).view(5, 3, 49))      # idx_g inverts idx_w on every 7x7 entry
 
 
 def test_oracle_epilogue_window_and_pitch():
@@ -99,13 +110,15 @@ def test_oracle_epilogue_window_and_pitch():
     g = torch.Generator().manual_seed(7)
     x, w = rnd(g, 1, 6, 6, 4), rnd(g, 3, 4, 9)
     b, sc, sh, res = rnd(g, 3), rnd(g, 3), rnd(g, 3), rnd(g, 1, 6, 6, 3)
-    r = O.evaluate(O.Problem(x, O.slots_fwd(w), O.forward_taps(3), 6, 6, bias=b, scale=sc, shift=sh, res=res, relu=True))
+    r = O.evaluate(O.from_geometry(x, O.slots_fwd(w), G.forward(6, 6, 3), bias=b, scale=sc, shift=sh, res=res, relu=True))
     conv = F.conv2d(nchw(x), w.view(3, 4, 3, 3), padding=1).permute(0, 2, 3, 1)
     assert torch.allclose(r.y, torch.relu((conv + b) * sc + sh + res), rtol=0, atol=1e-12)
     assert torch.allclose(r.stats, torch.cat([r.y.sum((0, 1, 2)), (r.y * r.y).sum((0, 1, 2))]))
     # one shifted tap of a rate-3 3x3 layer: tap (1, -1) of slot 6 on the rectangle whose source lies inside the image
     y0 = rnd(g, 1, 6, 6, 5)
-    p = O.Problem(x, O.slots_fwd(w), [(0 + 3, 3 - 3, 6)], 3, 3, y_H=6, y_W=6, y_pitch=5, out_off=(0, 3), res=y0[..., :3])
+    (geo,) = [q for q in G.shifted_taps(6, 6, 3) if q.taps[0][2] == 6]
+    assert (geo.taps, geo.Ho, geo.Wo, geo.out_off_y, geo.out_off_x) == ([(0 + 3, 3 - 3, 6)], 3, 3, 0, 3)
+    p = O.from_geometry(x, O.slots_fwd(w), geo, y_H=6, y_W=6, y_pitch=5, res=y0[..., :3])
     r = O.evaluate(p, y0=y0)
     want = y0.clone()
     want[:, 0:3, 3:6, :3] += torch.einsum("nyxc,oc->nyxo", x[:, 3:6, 0:3], w[:, :, 6])
@@ -123,7 +136,7 @@ def test_integer_operands_keep_the_row_strip_reference_representable(Cc, xvals):
     g = torch.Generator().manual_seed(Cc)
     W = 2048 // Cc
     x, w = O.int_operands(g, 2, 8, W, Cc, Cc, 9, xvals=xvals)
-    r = O.evaluate(O.Problem(x, O.slots_fwd(w), O.forward_taps(3), 8, W))
+    r = O.evaluate(O.from_geometry(x, O.slots_fwd(w), G.forward(8, W, 3)))
     assert bool((x != 0).all()) and bool((w != 0).all()) and bool((x == x.round()).all())
     O.assert_representable(r.y)
     O.assert_stats_exact(r.stats, Cc)
@@ -133,7 +146,7 @@ def test_cancelling_channel_pairs_bound_the_sum_and_still_see_a_misplaced_term()
     g = torch.Generator().manual_seed(9)
     x, w = O.int_operands(g, 2, 8, 64, 32, 32, 9, live=3)
     assert bool((x.abs() == 1).all()) and bool((w.abs() == 1).all())
-    p = O.Problem(x, O.slots_fwd(w), O.forward_taps(3), 8, 64)
+    p = O.from_geometry(x, O.slots_fwd(w), G.forward(8, 64, 3))
     r = O.evaluate(p)
     assert float(r.y.abs().max()) <= 2 * 3 * 9 and float(r.y.abs().max()) > 0
     # an 8-channel slot swapped with its neighbour in ONE pixel changes the nine outputs around it
@@ -161,43 +174,43 @@ def test_tile_config_query_answers_the_case_table_without_a_gpu(monkeypatch):
     row-strip problem, a pointwise problem, an invalid problem and one that fits no configuration."""
     import ctypes as C
 
-    import test_gpu_conv_exact as G
-    nv = G.nvmod()
+    import test_gpu_conv_exact as GT
+    nv = GT.nvmod()
     L = nv.lib()
     g = torch.Generator().manual_seed(0)
-    monkeypatch.setenv("HRP_PW_MIN_PIXELS", G.NO_PW)
+    monkeypatch.setenv("HRP_PW_MIN_PIXELS", GT.NO_PW)
     seen = set()
-    for name, c in G.TILE.items():
+    for name, c in GT.TILE.items():
         if c["N"] * c["H"] * c["W"] * c["cin"] > 1 << 20:       # (the big cases: shape only, no operands)
-            P = O.Problem(torch.zeros(c["N"], c["H"], c["W"], c["cin"], dtype=F64), torch.zeros(9 if c["kind"] == "k3" else 1, c["cout"], c["cin"], dtype=F64),
-                          O.forward_taps(3 if c["kind"] == "k3" else 1), c["H"], c["W"])
+            P = O.from_geometry(torch.zeros(c["N"], c["H"], c["W"], c["cin"], dtype=F64), torch.zeros(9 if c["kind"] == "k3" else 1, c["cout"], c["cin"], dtype=F64),
+                                G.forward(c["H"], c["W"], 3 if c["kind"] == "k3" else 1))
         else:
-            P = G.tile_problem(c, g)[0]
-        d = G.fill_desc(nv, nv.ConvDesc(), P, c["dt"], _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), G.rup(c["cin"], 8 if c["dt"] == "bf16" else 4))
+            P = GT.tile_problem(c, g)[0]
+        d = GT.fill_desc(nv, nv.ConvDesc(), P, c["dt"], _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), GT.rup(c["cin"], 8 if c["dt"] == "bf16" else 4))
         if c.get("stats", True):
             d.stats = 0x400000
         if c.get("res") == "y":
             d.res = d.y
         elif c.get("res") == "misaligned":
             d.res, d.res_pitch = 0x500002, P.Cout
-        assert G.route(nv, d) == (0, 0, c["cfg"]), (name, G.route(nv, d), L.hrp_last_error().decode())
+        assert GT.route(nv, d) == (0, 0, c["cfg"]), (name, GT.route(nv, d), L.hrp_last_error().decode())
         seen.add(c["cfg"] % 10000)
     assert seen == {2214, 2114, 1122, 1214, 1114}
     # a row-strip problem, a pointwise problem, an invalid problem, a problem no configuration fits
     x = torch.zeros(1, 8, 64, 32, dtype=F64)
-    P = O.Problem(x, torch.zeros(9, 32, 32, dtype=F64), O.forward_taps(3), 8, 64)
-    d = G.fill_desc(nv, nv.ConvDesc(), P, "bf16", _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), 32)
-    assert G.route(nv, d) == (32, 0, 0)
+    P = O.from_geometry(x, torch.zeros(9, 32, 32, dtype=F64), G.forward(8, 64, 3))
+    d = GT.fill_desc(nv, nv.ConvDesc(), P, "bf16", _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), 32)
+    assert GT.route(nv, d) == (32, 0, 0)
     d.x_pitch = 40                      # no longer dense rows: the tile program
-    assert G.route(nv, d) == (0, 0, 1114)
+    assert GT.route(nv, d) == (0, 0, 1114)
     d.x = 0x100008                      # misaligned input: hrp_conv2d_fwd refuses it
-    assert G.route(nv, d) == (0, 0, 0)
-    P1 = O.Problem(x, torch.zeros(1, 64, 32, dtype=F64), O.forward_taps(1), 8, 64)
-    d1 = G.fill_desc(nv, nv.ConvDesc(), P1, "bf16", _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), 32)
-    assert G.route(nv, d1) == (0, 0, 1122)
+    assert GT.route(nv, d) == (0, 0, 0)
+    P1 = O.from_geometry(x, torch.zeros(1, 64, 32, dtype=F64), G.forward(8, 64, 1))
+    d1 = GT.fill_desc(nv, nv.ConvDesc(), P1, "bf16", _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), 32)
+    assert GT.route(nv, d1) == (0, 0, 1122)
     monkeypatch.setenv("HRP_PW_MIN_PIXELS", "1")
-    assert G.route(nv, d1) == (0, 1, 0)
-    far = O.Problem(torch.zeros(1, 64, 64, 32, dtype=F64), torch.zeros(9, 64, 32, dtype=F64), O.forward_taps(3, 40), 64, 64)
-    df = G.fill_desc(nv, nv.ConvDesc(), far, "bf16", _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), 32)
-    assert G.route(nv, df) == (0, 0, 0)     # taps 40 pixels apart: beyond every tile that fits LDS (plan.py runs such layers as one-tap problems)
+    assert GT.route(nv, d1) == (0, 1, 0)
+    far = O.from_geometry(torch.zeros(1, 64, 64, 32, dtype=F64), torch.zeros(9, 64, 32, dtype=F64), G.forward(64, 64, 3, 1, 40))
+    df = GT.fill_desc(nv, nv.ConvDesc(), far, "bf16", _Ptr(0x100000), _Ptr(0x200000), _Ptr(0x300000), 32)
+    assert GT.route(nv, df) == (0, 0, 0)     # taps 40 pixels apart: beyond every tile that fits LDS (plan.py runs such layers as one-tap problems)
     assert L.hrp_conv_tile_config(None) == 0

@@ -29,6 +29,9 @@ import torch
 
 import conv_exact_oracle as O
 from conv_exact_oracle import F64
+
+import hrpe_amd  # noqa: F401
+from hrpe_amd import conv_geometry as G
 from test_gpu_pwconv import SHAPES as PW_SHAPES, desc1, pack1, small_problems_allowed  # noqa: F401  (autouse fixture: HRP_PW_MIN_PIXELS = 1)
 from test_gpu_rowconv import DEV, SLOTS, desc, mask_bits, nhwc, nvmod, pack, rup
 
@@ -65,17 +68,12 @@ def packn(nv, w, dt, transposed=False, pad_t=0):
 
 
 def fill_desc(nv, d, P, dt, x, w, y, x_pitch):
-    """The geometry, taps and element type of problem P into descriptor d (pointers: device tensors x, w, y)."""
+    """The geometry, taps and element type of problem P into descriptor d (pointers: device tensors x, w, y), by the function the
+    plans fill their descriptors with."""
     N, H, W, cin = P.x.shape
-    d.x, d.w, d.y, d.dtype = x.data_ptr(), w.data_ptr(), y.data_ptr(), code(nv, dt)
-    d.N, d.H, d.W, d.Cin, d.x_pitch = N, H, W, cin, x_pitch
-    d.Ho, d.Wo, d.Cout = P.Ho, P.Wo, P.Cout
-    d.y_H, d.y_W, d.y_pitch, d.res_pitch = P.y_H, P.y_W, P.y_pitch, P.y_pitch
-    d.out_stride, d.out_off_y, d.out_off_x, d.in_stride = P.out_stride, P.out_off[0], P.out_off[1], P.in_stride
-    d.ntaps, d.w_ntaps, d.w_cout_pad = len(P.taps), P.w.shape[0], rup(P.Cout, 32)
-    for i, (a, b, t) in enumerate(P.taps):
-        d.dy[i], d.dx[i], d.wtap[i] = a, b, t
-    return d
+    geo = G.ConvGeometry(P.Ho, P.Wo, P.in_stride, P.out_stride, P.out_off[0], P.out_off[1], P.taps, P.w.shape[0])
+    return G.fill_conv(geo, G.Operand(x.data_ptr(), N, H, W, cin, x_pitch), G.Operand(y.data_ptr(), N, P.y_H, P.y_W, P.Cout, P.y_pitch),
+                       code(nv, dt), d=d, w=w.data_ptr())
 
 
 def route(nv, d):
@@ -187,10 +185,10 @@ def row_operands(shape, transposed):
         big = N * H * W > 20000
         x, w = O.int_operands(g, N, H, W, Cc, Cc, 9, xvals=(1, -1) if big else ROW_XVALS[Cc], live=3 if big else None)
         if transposed:
-            P = O.Problem(x, O.slots_fwd(w), O.mirrored_taps(3), H, W)
+            P = O.from_geometry(x, O.slots_fwd(w), G.data_grad_s1(H, W, 3))
             wd = pack(nv, w.permute(1, 0, 2).contiguous().view(Cc, Cc, 3, 3).float())[1]
         else:
-            P = O.Problem(x, O.slots_fwd(w), O.forward_taps(3), H, W)
+            P = O.from_geometry(x, O.slots_fwd(w), G.forward(H, W, 3))
             wd = pack(nv, w.view(Cc, Cc, 3, 3).float())[0]
         _row_cache.clear()          # (one shape at a time: the largest tap sum is 34 MB)
         _row_cache[key] = (P, wd, O.accumulate(P))
@@ -234,9 +232,9 @@ def test_rowstrip_exact_permuted_tap_order():
     order = torch.randperm(9, generator=g).tolist()
     assert sigma != list(range(9)) and order != list(range(9))
     ws = w[:, :, sigma]
-    taps = [(O.TAPS3[sigma[s]][0], O.TAPS3[sigma[s]][1], s) for s in order]
+    taps = [(G.TAPS3[sigma[s]][0], G.TAPS3[sigma[s]][1], s) for s in order]
     P = O.Problem(x, O.slots_fwd(ws), taps, H, W)
-    ref = O.evaluate(O.Problem(x, O.slots_fwd(w), O.forward_taps(3), H, W)).y
+    ref = O.evaluate(O.from_geometry(x, O.slots_fwd(w), G.forward(H, W, 3))).y
     assert torch.equal(O.evaluate(P).y, ref)                   # the same convolution, by the oracle
     wd = pack(nv, ws.contiguous().view(Cc, Cc, 3, 3).float())[0]
     run_exact(nv, P, "bf16", wd, (Cc, 0, 0), g, what="row permuted taps")
@@ -320,7 +318,7 @@ def test_rowstrip_exact_forward_prologues(shape, mode):
     a = x * gamma + beta + (x2 if mode == 3 else 0)
     a = a.clamp_min(0)
     w = paired_weights(g, Cc, LIVE)
-    P = O.Problem(a, O.slots_fwd(w), O.forward_taps(3), H, W)
+    P = O.from_geometry(a, O.slots_fwd(w), G.forward(H, W, 3))
     R = O.evaluate(P, torch.full((N, H, W, Cc), SENTINEL, dtype=F64))
     O.assert_representable(R.out)
     O.assert_stats_exact(R.stats, Cc)
@@ -359,7 +357,7 @@ def test_rowstrip_exact_backward_prologue(shape, bits):
     gm = x * on
     a = gamma * (gm - k0 - x2 * k1)
     w = paired_weights(g, Cc, LIVE2)
-    P = O.Problem(a, O.slots_fwd(w), O.mirrored_taps(3), H, W)
+    P = O.from_geometry(a, O.slots_fwd(w), G.data_grad_s1(H, W, 3))
     prev = ints(g, (N, H, W, Cc), -3, 3)
     P.res = prev
     R = O.evaluate(P, prev)
@@ -392,7 +390,7 @@ def test_rowstrip_exact_reduce_epilogue(shape, bits):
     the BatchNorm input b) or by a bit mask, xhat = b (mean 0, invstd 1)."""
     nv, Cc, N, H, W, g, cnt = fused_setup(shape, 30 + bits)
     x, w = O.int_operands(g, N, H, W, Cc, Cc, 9, xvals=ROW_XVALS[Cc])
-    P = O.Problem(x, O.slots_fwd(w), O.mirrored_taps(3), H, W)
+    P = O.from_geometry(x, O.slots_fwd(w), G.data_grad_s1(H, W, 3))
     R = O.evaluate(P, torch.full((N, H, W, Cc), SENTINEL, dtype=F64))
     O.assert_representable(R.out)
     b = ints(g, (N, H, W, Cc), -2, 2)
@@ -476,25 +474,29 @@ def tile_problem(c, g):
     x, w = O.int_operands(g, N, H, W, cin, cout, nt, xvals=c.get("xvals", (1, -1)), live=c.get("live"))
     yp = c.get("y_pitch", 0)
     if kind in ("k3", "dil2", "k1"):
-        return O.Problem(x, O.slots_fwd(w), O.forward_taps(3 if nt == 9 else 1, 2 if kind == "dil2" else 1), H, W, y_pitch=yp), False, 0, w
+        return O.from_geometry(x, O.slots_fwd(w), G.forward(H, W, 3 if nt == 9 else 1, 1, 2 if kind == "dil2" else 1), y_pitch=yp), False, 0, w
     if kind == "k3s2":
-        return O.Problem(x, O.slots_fwd(w), O.forward_taps(3), (H - 1) // 2 + 1, (W - 1) // 2 + 1, in_stride=2, y_pitch=yp), False, 0, w
+        geo = G.forward(H, W, 3, 2)
+        assert (geo.Ho, geo.Wo, geo.in_stride) == ((H - 1) // 2 + 1, (W - 1) // 2 + 1, 2)
+        return O.from_geometry(x, O.slots_fwd(w), geo, y_pitch=yp), False, 0, w
     if kind == "stem":
-        return O.Problem(x, O.slots_fwd(w), O.stem_taps(), H, W, y_pitch=yp), False, 0, w
+        return O.from_geometry(x, O.slots_fwd(w), G.stem_s2d(H, W), y_pitch=yp), False, 0, w
     if kind == "par":       # x = the output gradient of a 3x3 stride-2 layer, y = the gradient of its (2H or 2H - 1) x (2W or 2W - 1) input
         (py, px), pad = c["cls"], 1 if c.get("padded") else 0
         yH, yW = 2 * H - (1 if c.get("odd") else 0), 2 * W - (1 if c.get("odd") else 0)
-        tl = O.class_taps(3, 1, py, px)
-        if pad:
-            tl = tl + [(tl[0][0], tl[0][1], 9)] * (4 - len(tl))
+        (geo,) = [q for q in G.data_grad_s2(yH, yW, 3, pad4=bool(pad)) if q.cls == 2 * py + px]
+        assert (geo.Ho, geo.Wo, geo.out_stride, geo.out_off_y, geo.out_off_x) == ((yH - py + 1) // 2, (yW - px + 1) // 2, 2, py, px)
+        assert (geo.Ho, geo.Wo) in ((H, W), (H - 1, W), (H, W - 1), (H - 1, W - 1)) and len(geo.taps) == (4 if pad else (1 + py) * (1 + px))
         slots = torch.cat([O.slots_fwd(w), torch.zeros(pad, cout, cin, dtype=F64)], 0)
-        return O.Problem(x, slots, tl, (yH - py + 1) // 2, (yW - px + 1) // 2, y_H=yH, y_W=yW, out_stride=2, out_off=(py, px), y_pitch=yp), True, pad, w
+        return O.from_geometry(x, slots, geo, y_H=yH, y_W=yW, y_pitch=yp), True, pad, w
     if kind == "k1s2bwd":
-        return O.Problem(x, O.slots_fwd(w), O.class_taps(1, 0, 0, 0), H, W, y_H=2 * H, y_W=2 * W - 1, out_stride=2, y_pitch=yp), True, 0, w
+        (geo,) = G.data_grad_s2(2 * H, 2 * W - 1, 1)
+        assert (geo.Ho, geo.Wo, geo.out_stride, geo.cls) == (H, W, 2, 0)
+        return O.from_geometry(x, O.slots_fwd(w), geo, y_H=2 * H, y_W=2 * W - 1, y_pitch=yp), True, 0, w
     if kind == "aspp":      # tap (a, b) = (1, -1) of a rate-6 3x3 layer on the rectangle whose source pixels exist, onto the centre tap's sum
-        r, (a, b), slot = 6, (1, -1), 6
-        y0_, y1_, x0_, x1_ = max(0, -a * r), min(H, H - a * r), max(0, -b * r), min(W, W - b * r)
-        return O.Problem(x, O.slots_fwd(w), [(y0_ + a * r, x0_ + b * r, slot)], y1_ - y0_, x1_ - x0_, y_H=H, y_W=W, out_off=(y0_, x0_), y_pitch=yp), False, 0, w
+        (geo,) = [q for q in G.shifted_taps(H, W, 6) if q.taps[0][2] == 6]
+        assert (geo.taps, geo.Ho, geo.Wo, geo.out_off_y, geo.out_off_x) == ([(6, 0, 6)], H - 6, W - 6, 0, 6)
+        return O.from_geometry(x, O.slots_fwd(w), geo, y_H=H, y_W=W, y_pitch=yp), False, 0, w
     raise ValueError(kind)
 
 
@@ -538,7 +540,7 @@ def test_pointwise_exact(shape, form, monkeypatch):
     for pw in (1, 0):
         if not pw:
             monkeypatch.setenv("HRP_PW_MIN_PIXELS", NO_PW)
-        P = O.Problem(x, O.slots_fwd(w), O.forward_taps(1), H, W)
+        P = O.from_geometry(x, O.slots_fwd(w), G.forward(H, W, 1))
         g2 = torch.Generator().manual_seed(cin + cout)
         res = None
         if form == "eval":
@@ -576,7 +578,7 @@ def test_batched_launch_exact():
         for kind, cin, cout, N, H, W in group:
             nt = 9 if kind in ("row", "tile") else 1
             x, w = O.int_operands(g, N, H, W, cin, cout, nt, xvals=(1, -1))
-            P = O.Problem(x, O.slots_fwd(w), O.forward_taps(3 if nt == 9 else 1), H, W, y_pitch=rup(cout, 8))
+            P = O.from_geometry(x, O.slots_fwd(w), G.forward(H, W, 3 if nt == 9 else 1), y_pitch=rup(cout, 8))
             y0 = torch.full((N, H, W, P.y_pitch), SENTINEL, dtype=F64)
             R = O.evaluate(P, y0)
             O.assert_representable(R.out)
