@@ -285,6 +285,17 @@ class JpegSegment(C.Structure):   # hrp_jpeg_segment
     _fields_ = [("off", C.c_int64), ("len", C.c_int64), ("image", C.c_int32), ("mcu0", C.c_int32)]
 
 
+TRACK_NO_ESTIMATE, TRACK_BAD_BOX, TRACK_LOST_OUT = 1, 2, 4             # HRP_TRACK_*
+TRACK_BBOX_EXTENDED, TRACK_BBOX_ORIGIN, TRACK_BBOX_STRICT = 0, 1, 2    # HRP_TRACK_BBOX_*
+TRACK_MAX_KP, TRACK_MAX_SIZE = 32, 4096
+
+
+class TrackGeom(C.Structure):     # hrp_track_geom
+    _fields_ = [("status", C.c_int32), ("crop_x0", C.c_int32), ("crop_y0", C.c_int32), ("crop_x1", C.c_int32), ("crop_y1", C.c_int32),
+                ("side", C.c_int32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("bbox_strict_bounded", (C.c_float * 4) * 2),
+                ("bbox_gt2d_extended", (C.c_float * 4) * 2), ("bbox_strict_bounded_original", C.c_float * 4)]
+
+
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
 # name -> argtypes (every function returns int unless noted); mirrors include/hrp.h one to one
 PROTOTYPES = {
@@ -377,6 +388,8 @@ PROTOTYPES = {
     "hrp_jpeg_decode_sync": [_P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
     "hrp_jpeg_decode_sync_stage": [_I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _Z, _P, _P],
     "hrp_jpeg_sync_scratch_bytes": [_Z, _I, _I],      # returns size_t (set in lib())
+    "hrp_track_prepare": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P],
+    "hrp_track_update": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -1,0 +1,143 @@
+"""Streaming pose tracker: the deployment counterpart of the three trainers.  A camera frame and the intrinsics go in, a pose comes
+out, and the crop of the NEXT frame is taken from this frame's estimate - all on the device (csrc/track.hip).
+
+The reference's loader crops around ANNOTATED key-points (lib/dataset/dream.py:171-216, 287-394; roboutils.py:59-156, 224-257;
+lib/utils/geometries.py:360-395) and its step derives ``k_values`` from the annotated boxes (lib/core/function.py:43-48, 88-98).
+``PoseTracker`` runs the same arithmetic on the key-points the model predicted for the previous frame:
+
+* ``prepare``  one launch (``hrp_track_prepare``): crop box, canvas, both views' K and boxes, ``k_values`` from the state, and the
+  crop + bilinear resize of both views straight from the frame;
+* the model    ``model(reg_images, root_images, k_values, other_K)``, ``RootNetwithRegInt.forward``'s signature, ``xyz_fk`` last;
+* ``update``   one launch (``hrp_track_update``): ``xyz_fk`` projected with ``K_original`` becomes the state.
+
+Nothing crosses PCIe except the frame, nothing here synchronises or reads a device value, every buffer is owned by the tracker and
+reused, so ``prepare`` and ``update`` can be captured in a graph.  A stream without a usable estimate (none yet, a box the loader
+would refuse, a prediction behind the camera or outside the frame) takes the whole frame and says so in ``status``; it recovers
+as soon as a prediction is usable again.  ``process_truncation`` is not part of the tracker: it crops inside the frame.  There is
+no CPU path: CPU tensors raise HrpError."""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from hrpe_amd import _native as nv
+
+TrackResult = namedtuple("TrackResult", "pose rot trans kp3d kp2d_original depth status k_values")
+
+
+class PoseTracker:
+    STATE_DTYPE = torch.float64
+
+    def __init__(self, model, robot, K_original, frame_hw, streams=1, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256),
+                 extend_ratio=(0.2, 0.13), use_origin_bbox=False, use_extended_bbox=True, reference_keypoint_id=3, min_inside=1,
+                 device=None):
+        """model: a callable with RootNetwithRegInt.forward's signature returning its tuple (xyz_fk last); a module is put in
+        eval().  robot: its ``nkp`` (or ``link_names``) gives the number of key-points.  K_original: [3, 3] or [streams, 3, 3].
+        frame_hw: (H, W) of every frame.  The bbox options select the box and K of ``k_values`` as prepare_batch does
+        (use_extended_bbox first, then use_origin_bbox, else the strict box).  reference_keypoint_id is the model's root key-point,
+        kept for the caller.  min_inside: how many predicted key-points must lie in the frame for the estimate to be used."""
+        device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if device.type != "cuda":
+            raise nv.HrpError(f"PoseTracker: {device} is not a GPU (there is no CPU path)")
+        nv.lib()
+        self.device, self.model, self.robot = device, model, robot
+        if isinstance(model, torch.nn.Module):
+            model.eval()
+        self.nkp = int(getattr(robot, "nkp", None) or len(robot.link_names))
+        self.B, (self.H, self.W) = int(streams), (int(frame_hw[0]), int(frame_hw[1]))
+        self.root_hw = (int(min(rootnet_resize_hw)), int(max(rootnet_resize_hw)))
+        self.other_hw = (int(min(other_resize_hw)), int(max(other_resize_hw)))
+        self.bbox_mode = nv.TRACK_BBOX_EXTENDED if use_extended_bbox else (nv.TRACK_BBOX_ORIGIN if use_origin_bbox else nv.TRACK_BBOX_STRICT)
+        self.reference_keypoint_id, self.min_inside = int(reference_keypoint_id), int(min_inside)
+        self._extend = (C.c_double * 2)(float(extend_ratio[0]), float(extend_ratio[1]))
+        if not (1 <= self.nkp <= nv.TRACK_MAX_KP) or self.B < 1:
+            raise nv.HrpError(f"PoseTracker: {self.nkp} key-points (1 .. {nv.TRACK_MAX_KP}), {self.B} streams")
+        for v in (self.H, self.W) + self.root_hw + self.other_hw:
+            if not (1 <= v <= nv.TRACK_MAX_SIZE):
+                raise nv.HrpError(f"PoseTracker: size {v}, want 1 .. {nv.TRACK_MAX_SIZE}")
+        K = torch.as_tensor(np.asarray(K_original, dtype=np.float64)).reshape(-1, 9)
+        if K.shape[0] not in (1, self.B):
+            raise nv.HrpError(f"PoseTracker: K_original for {K.shape[0]} streams, want 1 or {self.B}")
+        B, new = self.B, lambda *s, dt: torch.zeros(*s, dtype=dt, device=device)      # noqa: E731
+        self.K_original = K.expand(B, 9).to(device=device, dtype=torch.float32).contiguous()
+        self.kp2d, self.have = new(B, self.nkp, 2, dt=torch.float64), new(B, dt=torch.int32)
+        self.root_images = new(B, 3, *self.root_hw, dt=torch.uint8)
+        self.same = self.root_hw == self.other_hw              # one size: written once and aliased, as DreamDataset.to_device does
+        self.reg_images = self.root_images if self.same else new(B, 3, *self.other_hw, dt=torch.uint8)
+        self.root_K, self.other_K = new(B, 3, 3, dt=torch.float32), new(B, 3, 3, dt=torch.float32)
+        self.k_values, self.status = new(B, dt=torch.float32), new(B, dt=torch.int32)
+        self.geom = new(B, C.sizeof(nv.TrackGeom), dt=torch.uint8)                       # hrp_track_geom records
+        self._geom_status = self.geom.view(torch.int32)[:, 0]
+        self.kp2d_original = new(B, self.nkp, 2, dt=torch.float32)
+        self.jpeg_status = None
+
+    def reset(self, kp2d=None, streams=None):
+        """Seed the estimate: kp2d [B, nkp, 2] in original-image pixels (float64 is kept bit for bit), or None for no estimate.
+        streams: the indices it applies to (kp2d then has one row per index); the other streams keep their state."""
+        idx = torch.arange(self.B) if streams is None else torch.as_tensor(list(streams), dtype=torch.int64)
+        idx = idx.to(self.device)
+        if kp2d is None:
+            self.have.index_fill_(0, idx, 0)
+            return
+        kp = torch.as_tensor(kp2d, dtype=torch.float64).to(self.device)
+        if tuple(kp.shape) != (idx.numel(), self.nkp, 2):
+            raise nv.HrpError(f"PoseTracker.reset: kp2d {tuple(kp.shape)}, want {(idx.numel(), self.nkp, 2)}")
+        self.kp2d.index_copy_(0, idx, kp)
+        self.have.index_fill_(0, idx, 1)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def prepare(self, frames):
+        """frames: uint8 [B, H, W, 3] on the device.  Returns the model's inputs (tensors owned by the tracker, rewritten by the
+        next call): root_images / reg_images uint8 [B, 3, h, w], root_K / other_K [B, 3, 3], k_values [B], geom [B, 112] uint8
+        (hrp_track_geom records: crop box, canvas, boxes, status)."""
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
+            raise nv.HrpError("PoseTracker: frames must be a uint8 GPU tensor (there is no CPU path)")
+        if tuple(frames.shape) != (self.B, self.H, self.W, 3):
+            raise nv.HrpError(f"PoseTracker: frames {tuple(frames.shape)}, want {(self.B, self.H, self.W, 3)}")
+        frames = frames.contiguous()
+        nv.call("hrp_track_prepare", frames.data_ptr(), self.kp2d.data_ptr(), self.have.data_ptr(), self.K_original.data_ptr(), self.B,
+                self.H, self.W, self.nkp, self.root_images.data_ptr(), self.root_hw[0], self.root_hw[1],
+                None if self.same else self.reg_images.data_ptr(), self.other_hw[0], self.other_hw[1], self._extend, self.bbox_mode,
+                self.root_K.data_ptr(), self.other_K.data_ptr(), self.k_values.data_ptr(), self.geom.data_ptr(), self._stream())
+        self.status.copy_(self._geom_status)
+        return dict(root_images=self.root_images, reg_images=self.reg_images, root_K=self.root_K, other_K=self.other_K,
+                    k_values=self.k_values, geom=self.geom)
+
+    def update(self, pred):
+        """Apply the model's output (its tuple, or xyz_fk [B, nkp, 3] itself) to the state.  Returns kp2d_original [B, nkp, 2] fp32;
+        ``status`` gains HRP_TRACK_LOST_OUT where the prediction was refused."""
+        xyz = pred[-1] if isinstance(pred, (tuple, list)) else pred
+        if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
+            raise nv.HrpError("PoseTracker.update: xyz_fk must be a GPU tensor (there is no CPU path)")
+        if tuple(xyz.shape) != (self.B, self.nkp, 3):
+            raise nv.HrpError(f"PoseTracker.update: xyz_fk {tuple(xyz.shape)}, want {(self.B, self.nkp, 3)}")
+        xyz = xyz.detach().float().contiguous()
+        nv.call("hrp_track_update", xyz.data_ptr(), self.K_original.data_ptr(), self.B, self.nkp, self.W, self.H, self.min_inside,
+                self.kp2d.data_ptr(), self.have.data_ptr(), self.kp2d_original.data_ptr(), self.status.data_ptr(), self._stream())
+        return self.kp2d_original
+
+    def decode(self, files):
+        """A list of JPEG files' bytes -> uint8 [B, H, W, 3] on the device through dream.decode_frames: baseline files on the GPU,
+        the others by Pillow.  The decode's status tensor is left in ``jpeg_status`` (jpeg.check_status reads it, and
+        synchronises)."""
+        from hrpe_amd.lib.dataset import dream
+        enc = [dream._Encoded(bytes(f)) for f in files]
+        frames, self.jpeg_status = dream.decode_frames([e.jpeg for e in enc], np.stack([e.hdr for e in enc]), [e.host for e in enc],
+                                                       self.device)
+        return frames
+
+    def step(self, frames):
+        """One frame per stream: prepare, the model, update.  frames: uint8 [B, H, W, 3] on the device, or a list of JPEG bytes.
+        Returns TrackResult(pose, rot, trans, kp3d, kp2d_original, depth, status, k_values), device tensors; kp2d_original,
+        status and k_values are the tracker's own buffers."""
+        if isinstance(frames, (list, tuple)):
+            frames = self.decode(frames)
+        p = self.prepare(frames)
+        with torch.no_grad():
+            out = tuple(self.model(p["reg_images"], p["root_images"], p["k_values"], p["other_K"]))
+        kp2d = self.update(out)
+        return TrackResult(pose=out[0], rot=out[1], trans=out[2], kp3d=out[-1], kp2d_original=kp2d, depth=out[4] if len(out) > 4 else None, status=self.status,
+                           k_values=self.k_values)

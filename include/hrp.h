@@ -67,6 +67,13 @@
  *                                                     lib/dataset/dream.py:110
  *   hrp_jpeg_decode_sync      the same with a long segment (a file without restart markers) decoded by one workgroup from
  *                             speculative start points
+ *   hrp_track_prepare         the loader's crop / K / box / k_value geometry (get_bbox, resize_image, get_K_crop_resize,
+ *                             bbox_transform, get_extended_bbox, k_values) from the LAST pose estimate instead of the annotation,
+ *                             and the crop + bilinear resize of both views straight from the frame, in one launch
+ *                                                     lib/dataset/dream.py:171-216, 287-394; roboutils.py:59-156, 224-257;
+ *                                                     lib/utils/geometries.py:360-395; lib/core/function.py:43-48, 88-98
+ *   hrp_track_update          the projection of the model's FK key-points into the original image, which becomes the estimate the
+ *                             next frame is cropped from          lib/utils/geometries.py:100-115; lib/dataset/dream.py:171-216
  */
 #ifndef HRP_H
 #define HRP_H
@@ -1089,6 +1096,51 @@ int hrp_jpeg_decode_sync_stage(int stage, int guess_unit, int guess_k, const hrp
                                const hrp_jpeg_segment* short_segments_dev, int nshort, const hrp_jpeg_segment* long_segments_dev, int nlong,
                                int subseq_bytes, const uint8_t* bytes, size_t nbytes, int16_t* coef, size_t ncoef, uint8_t* planes,
                                size_t nplanes, uint8_t* frames, size_t nframes, void* scratch, size_t nscratch, int32_t* status, void* stream);
+
+/* Streaming pose tracker (csrc/track.hip; the arithmetic is csrc/track_core.h, the same functions for the kernels and for a host
+ * compiler, tests/track_host_check.cpp): this frame's crop from the last frame's estimate, on the device.  Replaces what the
+ * reference's loader computes from ANNOTATED key-points (lib/dataset/dream.py:171-216, 287-394; roboutils.py:59-156, 224-257;
+ * lib/utils/geometries.py:360-395) and the k_values of the step (lib/core/function.py:43-48, 88-98), fed the key-points that the
+ * model predicted for the previous frame.  process_truncation is not part of it: the tracker crops inside the frame.
+ *
+ * hrp_track_prepare, one launch: every workgroup derives its stream's hrp_track_geom once (float64, the loader's order of
+ * operations, int() where the host truncates, no contraction) and then writes its share of the pixels of both views, reading the
+ * frame directly (hrp_dream_crop_resize's arithmetic without the enhancement tail; no scratch copy of the frame).
+ *   frames [B, H, W, 3] uint8; state_kp2d [B, nkp, 2] float64, the estimate in ORIGINAL-image pixels; state_have [B] int32 (0: no
+ *   estimate, the whole frame is taken); K_original [B, 9] fp32 row-major pinhole intrinsics (no skew);
+ *   out_root [B, 3, h0, w0] uint8; out_other [B, 3, h1, w1] uint8 or NULL when the two views have one size (the caller aliases
+ *   them; K_other then equals K_root); h = min, w = max of the reference's resize_hw, whose first entry bounds x and whose second
+ *   bounds y in the boxes, as there; extend_ratio: two host doubles (dream.py's extend_ratio);
+ *   bbox_mode: the box and K that k_values takes (function.py:43-48): HRP_TRACK_BBOX_EXTENDED (use_extended_bbox),
+ *   HRP_TRACK_BBOX_ORIGIN (use_origin_bbox) or HRP_TRACK_BBOX_STRICT;
+ *   K_root, K_other [B, 9] fp32, k_values [B] fp32, geom [B] hrp_track_geom: outputs.
+ * The estimate of a stream is treated as absent for this frame - whole frame, HRP_TRACK_NO_ESTIMATE | HRP_TRACK_BAD_BOX - when its
+ * crop box fails the loader's check 0 <= x0 < x1 <= W, 0 <= y0 < y1 <= H (dream.py:318), when k_value is not finite and positive, or
+ * when an input is not finite; HRP_TRACK_NO_ESTIMATE alone means state_have was 0.  Every float -> int conversion is range-checked
+ * first, and every frame index is tested against W, H immediately before its load, whatever the record says.
+ *
+ * hrp_track_update, one launch: kp2d = (fx X / Z + cx, fy Y / Z + cy) in float64 of xyz_fk [B, nkp, 3] fp32 (camera frame) into
+ * state_kp2d and, as fp32, kp2d_out [B, nkp, 2]; state_have = 1 iff every coordinate is finite, every Z > 0 and at least min_inside
+ * key-points lie in [0, W) x [0, H), otherwise 0 and HRP_TRACK_LOST_OUT is ORed into status [B] (which the caller initialised, e.g.
+ * from hrp_track_geom.status).
+ * Grids depend on the host arguments only, caller-owned buffers, no host synchronisation: graph-capturable. */
+enum { HRP_TRACK_NO_ESTIMATE = 1, HRP_TRACK_BAD_BOX = 2, HRP_TRACK_LOST_OUT = 4 };
+enum { HRP_TRACK_BBOX_EXTENDED = 0, HRP_TRACK_BBOX_ORIGIN = 1, HRP_TRACK_BBOX_STRICT = 2 };
+#define HRP_TRACK_MAX_KP 32
+#define HRP_TRACK_MAX_SIZE 4096
+typedef struct {
+  int32_t status;                                   /* HRP_TRACK_NO_ESTIMATE | HRP_TRACK_BAD_BOX */
+  int32_t crop_x0, crop_y0, crop_x1, crop_y1;       /* the crop box in the frame (get_bbox, strict) */
+  int32_t side, off_x, off_y;                       /* resize_image's square canvas and the crop's offset in it */
+  float bbox_strict_bounded[2][4];                  /* per view (0 root, 1 other) */
+  float bbox_gt2d_extended[2][4];                   /* per view */
+  float bbox_strict_bounded_original[4];
+} hrp_track_geom;
+int hrp_track_prepare(const uint8_t* frames, const double* state_kp2d, const int32_t* state_have, const float* K_original, int B, int H,
+                      int W, int nkp, uint8_t* out_root, int h0, int w0, uint8_t* out_other, int h1, int w1, const double* extend_ratio,
+                      int bbox_mode, float* K_root, float* K_other, float* k_values, hrp_track_geom* geom, void* stream);
+int hrp_track_update(const float* xyz_fk, const float* K_original, int B, int nkp, int W, int H, int min_inside, double* state_kp2d,
+                     int32_t* state_have, float* kp2d_out, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
