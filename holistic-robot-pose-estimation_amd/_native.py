@@ -69,6 +69,17 @@ class WgradFoldDesc(C.Structure):
                 ("dw_tap_off", C.c_int32), ("accumulate", C.c_int32), ("reserved", C.c_int32)]
 
 
+WGRAD_FOUR_WAVE, WGRAD_EIGHT_WAVE_BF16, WGRAD_EIGHT_WAVE_F32X3 = range(3)
+
+
+class WgradConfig(C.Structure):
+    """hrp_wgrad_config (include/hrp.h): what a weight-gradient launch will run."""
+    _fields_ = [("program", C.c_int32), ("arrange", C.c_int32), ("nks", C.c_int32), ("BM", C.c_int32),
+                ("TI", C.c_int32), ("TH", C.c_int32), ("TW", C.c_int32), ("ring", C.c_int32), ("xmode", C.c_int32),
+                ("G", C.c_int32), ("ntiles", C.c_int32), ("pairs", C.c_int32), ("use_ws", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class Sim2RealLossDesc(C.Structure):
     _fields_ = [("rendered", C.c_void_p), ("seg", C.c_void_p), ("kp3d", C.c_void_p), ("kp3d_int", C.c_void_p),
                 ("B", C.c_int32), ("HW", C.c_int32), ("K", C.c_int32), ("mask_loss", C.c_int32),
@@ -355,6 +366,8 @@ PROTOTYPES = {
     "hrp_rot6d_compose_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "hrp_wgrad_fold_desc_of": [C.POINTER(WgradDesc), C.POINTER(WgradFoldDesc)],
     "hrp_batch_wgrad_fold_descs": [_P, C.POINTER(BatchInfo), C.POINTER(WgradFoldDesc)],
+    "hrp_wgrad_config_of": [C.POINTER(WgradDesc), C.POINTER(WgradConfig)],
+    "hrp_batch_wgrad_configs": [_P, C.POINTER(BatchInfo), C.POINTER(WgradConfig)],
     "hrp_block_channels": [C.POINTER(BlockDesc)],
     "hrp_block_prepare": [_P, _I, _P, C.POINTER(BlockInfo)],
     "hrp_block_launch": [_P, C.POINTER(BlockInfo), _P],

@@ -1371,30 +1371,43 @@ static int64_t wgrad_ws_bytes(const hrp_wgrad_desc& d) {
   return wgrad_ws_bytes_nb<T, NT, 1>(d);
 }
 
+// bf16 / fp32x3: k-steps of 16 pixels per wave and tile, unrolled at compile time (fp32x3 tiles stop at 128 pixels); fp32: 0
+template <typename T>
+static inline int wgrad_nks(const int BM) { return std::is_same<T, float>::value ? 0 : BM / 64; }
+
+// What a launch of its own runs: the tiling and whether the slabs go through the workspace (launch_wgrad_nb, hrp_wgrad_config_of)
+template <typename T, int NT, int NB>
+static int wgrad_plan_single(const hrp_wgrad_desc& d, WgradTiling& t) {
+  const int rc = wgrad_tiling<T, NT, NB>(d, t);
+  if (rc != HRP_OK) return rc;
+  const int64_t need = (int64_t)t.G * t.n_cob * t.n_cib * (NT * NB * NB) * 1024 * 4;
+  t.use_ws = (d.workspace && d.workspace_bytes >= need) ? 1 : 0;
+  if (!t.use_ws && !d.accumulate && d.dw_tap_stride > 0 && d.dw_tap_stride != d.ntaps) {
+    set_error("wgrad: a tap group without a workspace must accumulate (the caller zeroes dw)");
+    return HRP_ERR_ARG;
+  }
+  return HRP_OK;
+}
+
 template <typename T, int NT, int NB>
 static int launch_wgrad_nb(const hrp_wgrad_desc& d, hipStream_t s) {
   constexpr int NTE = NT * NB * NB;
   WgradTiling t{};
-  int rc = wgrad_tiling<T, NT, NB>(d, t);
+  int rc = wgrad_plan_single<T, NT, NB>(d, t);
   if (rc != HRP_OK) return rc;
   const int pairs = t.n_cob * t.n_cib;
-  const int64_t need = (int64_t)t.G * pairs * NTE * 1024 * 4;
-  t.use_ws = (d.workspace && d.workspace_bytes >= need) ? 1 : 0;
-  if (!t.use_ws && !d.accumulate) {
-    if (d.dw_tap_stride > 0 && d.dw_tap_stride != d.ntaps) {
-      set_error("wgrad: a tap group without a workspace must accumulate (the caller zeroes dw)");
-      return HRP_ERR_ARG;
-    }
-    zero_async(d.dw, sizeof(float) * (size_t)d.Cout * d.dw_cin * d.ntaps, s);
-  }
+  if (!t.use_ws && !d.accumulate) zero_async(d.dw, sizeof(float) * (size_t)d.Cout * d.dw_cin * d.ntaps, s);
   void (*kern)(const hrp_wgrad_desc, const WgradTiling) = nullptr;
-  if constexpr (Elem<T>::SZ == 2 || std::is_same<T, f32x3_t>::value) {
-    // bf16 / fp32x3: k-steps of 16 pixels per wave and tile = BM / 64, unrolled at compile time
-    if constexpr (std::is_same<T, f32x3_t>::value) kern = t.BM == 128 ? conv_wgrad_kernel<T, NT, 2, NB> : conv_wgrad_kernel<T, NT, 1, NB>;
-    else kern = t.BM == 256 ? conv_wgrad_kernel<T, NT, 4, NB> : t.BM == 128 ? conv_wgrad_kernel<T, NT, 2, NB> : conv_wgrad_kernel<T, NT, 1, NB>;
-  } else {
+  if constexpr (std::is_same<T, float>::value) {
     kern = conv_wgrad_kernel<T, NT, 0, NB>;
+  } else {
+    switch (wgrad_nks<T>(t.BM)) {
+      case 4: if constexpr (Elem<T>::SZ == 2) { kern = conv_wgrad_kernel<T, NT, 4, NB>; } break;
+      case 2: kern = conv_wgrad_kernel<T, NT, 2, NB>; break;
+      default: kern = conv_wgrad_kernel<T, NT, 1, NB>; break;
+    }
   }
+  HRP_REQUIRE(kern, "wgrad: no program for %d-pixel tiles", t.BM);
   static bool attr_set[5] = {};   // per (T, NT, NB) instantiation, indexed by BM / 64
   if (!attr_set[t.BM / 64]) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1559,7 +1572,7 @@ static int wgrad_plan_one(const hrp_wgrad_desc& d, WgradProblem& P, int budget, 
     rc = wgrad_tiling<T, NT, 1>(d, P.t, budget);
   }
   if (rc != HRP_OK) return rc;
-  P.nks = std::is_same<T, float>::value ? 0 : P.t.BM / 64;
+  P.nks = wgrad_nks<T>(P.t.BM);
   P.nte = NT * P.nb * P.nb;
   P.pairs = P.t.n_cob * P.t.n_cib;
   P.fold_pairs = P.pairs; P.fold_n_cib = P.t.n_cib; P.fold_nb = P.nb;
@@ -1752,7 +1765,64 @@ static int fold_desc_t(const hrp_wgrad_desc& d, hrp_wgrad_fold_desc* out) {
   return fold_desc_nb<T, NT, 1>(d, out);
 }
 
+// ---- what a launch will run (hrp_wgrad_config) ------------------------------------------------------------------
+// nb as in WgradProblem: 1 / 2 the four-wave program's NB, 3 / 6 the eight-wave programs with PAIRS = nb - 2
+static hrp_wgrad_config make_config(const hrp_wgrad_desc& d, const WgradTiling& t, int nks, int nb) {
+  hrp_wgrad_config c{};
+  c.program = nb < 3 ? HRP_WGRAD_FOUR_WAVE : d.dtype == HRP_F32X3 ? HRP_WGRAD_EIGHT_WAVE_F32X3 : HRP_WGRAD_EIGHT_WAVE_BF16;
+  c.arrange = nb < 3 ? nb : nb - 2;
+  c.nks = nks; c.BM = t.BM;
+  c.TI = t.TI; c.TH = t.TH; c.TW = t.TW;
+  c.ring = c.program == HRP_WGRAD_EIGHT_WAVE_BF16 ? t.ring : 0; c.xmode = t.xmode;
+  c.G = t.G; c.ntiles = t.ntiles; c.pairs = t.n_cob * t.n_cib;
+  c.use_ws = t.use_ws;
+  return c;
+}
+template <typename T, int NT, int NB>
+static int config_nb(const hrp_wgrad_desc& d, hrp_wgrad_config* out) {
+  WgradTiling t{};
+  const int rc = wgrad_plan_single<T, NT, NB>(d, t);
+  if (rc != HRP_OK) return rc;
+  *out = make_config(d, t, wgrad_nks<T>(t.BM), NB);
+  return HRP_OK;
+}
+template <typename T, int NT>
+static int config_t(const hrp_wgrad_desc& d, hrp_wgrad_config* out) {
+  if constexpr (can_nb2<T, NT>()) {
+    if (want_nb2(d)) return config_nb<T, NT, 2>(d, out);
+  }
+  return config_nb<T, NT, 1>(d, out);
+}
+
 }  // namespace hrp
+
+extern "C" int hrp_wgrad_config_of(const hrp_wgrad_desc* d, hrp_wgrad_config* out) {
+  using namespace hrp;
+  HRP_REQUIRE(out, "wgrad config: null pointer");
+  const int crc = wgrad_check(d);
+  if (crc != HRP_OK) return crc;
+  if (d->dtype == HRP_F32) {
+    if (d->ntaps == 1) return config_t<float, 1>(*d, out);
+    if (d->ntaps == 4) return config_t<float, 4>(*d, out);
+    return config_t<float, 9>(*d, out);
+  }
+  if (d->dtype == HRP_F32X3) {
+    if (d->ntaps == 1) return config_t<f32x3_t, 1>(*d, out);
+    if (d->ntaps == 4) return config_t<f32x3_t, 4>(*d, out);
+    return config_t<f32x3_t, 9>(*d, out);
+  }
+  if (d->ntaps == 1) return config_t<bf16_t, 1>(*d, out);
+  if (d->ntaps == 4) return config_t<bf16_t, 4>(*d, out);
+  return config_t<bf16_t, 9>(*d, out);
+}
+
+extern "C" int hrp_batch_wgrad_configs(const void* table_host, const hrp_batch_info* info, hrp_wgrad_config* out) {
+  using namespace hrp;
+  HRP_REQUIRE(table_host && info && out && info->family == HRP_BATCH_WGRAD, "wgrad config: needs a prepared HRP_BATCH_WGRAD table");
+  const WgradProblem* tab = (const WgradProblem*)table_host;
+  for (int i = 0; i < info->n; ++i) out[i] = make_config(tab[i].d, tab[i].t, tab[i].nks, tab[i].nb);
+  return HRP_OK;
+}
 
 extern "C" int hrp_wgrad_fold_desc_of(const hrp_wgrad_desc* d, hrp_wgrad_fold_desc* out) {
   using namespace hrp;

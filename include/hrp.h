@@ -224,7 +224,8 @@ typedef struct hrp_conv_desc {
 } hrp_conv_desc;
 
 /* Weight gradient: dW[co][ci][t] (+)= sum_{n,oy,ox} dy[n,oy,ox,co] * x[n, oy*IS+dy[t], ox*IS+dx[t], ci],
- * written in fp32 straight into the PyTorch-shaped gradient tensor [Cout][Cin_w][ntaps] (Cin_w >= Cin real). */
+ * written in fp32 straight into the PyTorch-shaped gradient tensor [Cout][dw_cin][ntaps], dw_cin <= Cin: the real input
+ * channels.  Channels of x at or beyond dw_cin (padding up to Cin) and lanes of dy at or beyond Cout are masked at the store. */
 typedef struct hrp_wgrad_desc {
   const void* x;       /* forward input  [N, H, W, x_pitch] */
   const void* dy;      /* output grad    [N, Ho, Wo, dy_pitch] */
@@ -536,6 +537,23 @@ int hrp_batch_launch(const void* table_dev, const hrp_batch_info* info, void* st
  * choose for d) / of the n problems of a prepared HRP_BATCH_WGRAD table (host copy), in the CALLER's order */
 int hrp_wgrad_fold_desc_of(const hrp_wgrad_desc* d, hrp_wgrad_fold_desc* out);
 int hrp_batch_wgrad_fold_descs(const void* table_host, const hrp_batch_info* info, hrp_wgrad_fold_desc* out);
+/* What a weight-gradient launch will run (host only, no HIP call; answered by the launcher's own tiling code): of a single
+ * launch (hrp_conv2d_bwd_weight on d, an invalid d returns that call's error) / of the n problems of a prepared
+ * HRP_BATCH_WGRAD table (host copy), in the CALLER's order. */
+typedef enum { HRP_WGRAD_FOUR_WAVE = 0, HRP_WGRAD_EIGHT_WAVE_BF16 = 1, HRP_WGRAD_EIGHT_WAVE_F32X3 = 2 } hrp_wgrad_program;
+typedef struct hrp_wgrad_config {
+  int32_t program;     /* hrp_wgrad_program */
+  int32_t arrange;     /* four-wave: NB, 1 / 2 = 32 / 64-channel blocks.  eight-wave: PAIRS, 1 / 4 32 x 32 pairs per workgroup */
+  int32_t nks, BM;     /* k-steps of 16 pixels per wave and tile (0: HRP_F32, whose k-loop is not unrolled); pixels per tile */
+  int32_t TI, TH, TW;  /* images, rows and columns of a pixel tile */
+  int32_t ring, xmode; /* stage buffers of the eight-wave bf16 tile ring (else 0); workgroup numbering 0 / 1 / 2 */
+  int32_t G, ntiles;   /* workgroups (= partial slabs) per channel-block pair; pixel tiles they share: g walks g, g + G, .. */
+  int32_t pairs;       /* channel-block pairs: the launch has G * pairs workgroups */
+  int32_t use_ws;      /* 1: partial slabs in the workspace, then the fold.  0: fp32 atomics into dw */
+  int32_t reserved[3];
+} hrp_wgrad_config;
+int hrp_wgrad_config_of(const hrp_wgrad_desc* d, hrp_wgrad_config* out);
+int hrp_batch_wgrad_configs(const void* table_host, const hrp_batch_info* info, hrp_wgrad_config* out);
 
 /* ---- segmentation-mask network of the self-supervised trainer (BASELINE config 5), the parts that are not convolutions -------
  * (reference lib/models/ctrnet/mask_inference.py:44-57 preprocess_img_tensor, keypoint_seg_resnet.py:134-149, CtRNet.py:102-111;

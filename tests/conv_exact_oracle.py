@@ -216,6 +216,65 @@ def int_operands(g, N, H, W, cin, cout, ntaps, xvals=(1, -1), wvals=(1, -1), liv
     return x, w
 
 
+# ---- operands of the exact weight-gradient tests ----------------------------------------------------------------------------------------
+# Magnitudes (signs are drawn).  BF16_INTS are bf16 numbers.  WIDE_INTS are not: they need 9 or 10 significant bits, so a path that
+# rounds an fp32 operand to bf16 changes them - yet each is hi + lo with hi = bf16(v), lo = bf16(v - hi) exactly, so the fp32x3 kernels'
+# hi.hi + hi.lo + lo.hi is the exact product with a bf16 integer (the dropped lo.lo term is zero because the other operand's lo is).
+BF16_INTS = (1, 2, 3)
+WIDE_INTS = (257, 259, 1001)
+WIDE_INTS_SMALL = (257, 259, 261)
+EXACT_LIMIT = 2 ** 24
+
+
+def split_planes(v):
+    """The fp32x3 kernels' operand split, with torch on the CPU: hi = rne_bf16(v), lo = rne_bf16(v - hi)."""
+    v = v.to(torch.float32)
+    hi = v.to(torch.bfloat16).to(torch.float32)
+    lo = (v - hi).to(torch.bfloat16).to(torch.float32)
+    return hi, lo
+
+
+def assert_value_class(t, wide, what):
+    """wide: every value differs from its bf16 rounding AND equals hi + lo; otherwise every value is a bf16 number."""
+    hi, lo = split_planes(t)
+    assert bool((t != 0).all()) and bool((t == t.round()).all()), f"{what}: operands are non-zero integers"
+    if wide:
+        assert bool((hi.to(F64) != t.to(F64)).all()), f"{what}: some values are bf16 numbers - a rounded operand would pass"
+        assert bool(((hi + lo).to(F64) == t.to(F64)).all()), f"{what}: some values are not hi + lo - the three products are not exact"
+    else:
+        assert bool((hi.to(F64) == t.to(F64)).all()) and bool((lo == 0).all()), f"{what}: some values are no bf16 numbers"
+
+
+def wgrad_values(dt, split, pixels):
+    """(x magnitudes, dy magnitudes) of a weight-gradient problem summed over `pixels` positions: the richest sets that keep
+    pixels * max|x| * max|dy| + 7 below 2^24.  bf16: bf16 integers.  f32 / f32x3: the operand `split` ("x" / "dy") comes from the
+    integers that are no bf16 numbers, the other from bf16 integers."""
+    if dt == "bf16":
+        cands = [(BF16_INTS, BF16_INTS)]
+    else:
+        cands = [(WIDE_INTS, BF16_INTS), (WIDE_INTS_SMALL, BF16_INTS), (WIDE_INTS_SMALL, (1,))]
+    for wide, small in cands:
+        if pixels * max(wide) * max(small) + 7 < EXACT_LIMIT:
+            return (wide, small) if split == "x" or dt == "bf16" else (small, wide)
+    raise AssertionError(f"{pixels} pixels: no value set keeps the sums below 2^24")
+
+
+def signed(g, shape, mags):
+    return pick(g, shape, tuple(mags) + tuple(-m for m in mags))
+
+
+def wgrad_operands(g, dt, split, N, H, W, cin, Ho, Wo, cout):
+    """x [N, H, W, cin], dy [N, Ho, Wo, cout] as float64 integers of the problem's value class."""
+    xm, dm = wgrad_values(dt, split, N * Ho * Wo)
+    return signed(g, (N, H, W, cin), xm), signed(g, (N, Ho, Wo, cout), dm)
+
+
+def assert_wgrad_exact(x, dy, dw0, pixels):
+    """The precondition of an exact weight gradient, on the operands alone."""
+    bound = pixels * float(x.abs().max()) * float(dy.abs().max()) + float(dw0.abs().max())
+    assert bound < EXACT_LIMIT, f"N Ho Wo max|x| max|dy| + max|dw0| = {bound} >= 2^24: the test's inputs are wrong"
+
+
 def representable(t, dtype=torch.bfloat16):
     return bool((t.to(dtype).to(F64) == t.to(F64)).all())
 

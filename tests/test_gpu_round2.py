@@ -198,7 +198,7 @@ def test_deferred_wgrad_fold_equals_immediate(dtype):
         info = nv.BatchInfo()
         nv.check(L.hrp_batch_prepare(nv.BATCH_WGRAD, arr, 3, None, C.byref(info)), "query")
         for i, d in enumerate(arr):
-            ws = torch.zeros(int(info.ws_bytes[i]) // 4 + 4, device=DEV)
+            ws = torch.full((int(info.ws_bytes[i]) // 4 + 4,), float("nan"), device=DEV)      # a slab element no workgroup writes folds as NaN
             d.workspace, d.workspace_bytes = ws.data_ptr(), int(info.ws_bytes[i])
             wss.append(ws)
         host = (C.c_char * int(L.hrp_batch_table_bytes(nv.BATCH_WGRAD, 3)))()
@@ -216,7 +216,7 @@ def test_deferred_wgrad_fold_equals_immediate(dtype):
         d.dw = dw.data_ptr()
         need = int(L.hrp_wgrad_workspace_bytes(C.byref(d)))
         assert need > 0
-        ws = torch.zeros(need // 4 + 4, device=DEV)
+        ws = torch.full((need // 4 + 4,), float("nan"), device=DEV)
         d.workspace, d.workspace_bytes = ws.data_ptr(), need
         nv.call("hrp_conv2d_bwd_weight", C.byref(d), None)
         wss.append(ws)

@@ -66,7 +66,7 @@ def test_eight_wave_program_in_a_mixed_batch(phase, x3):
     nv.check(L.hrp_batch_prepare(nv.BATCH_WGRAD, arr, n, None, C.byref(info)), "query")
     wss = []
     for i, d in enumerate(arr):
-        ws = torch.zeros(int(info.ws_bytes[i]) // 4 + 4, device=DEV)
+        ws = torch.full((int(info.ws_bytes[i]) // 4 + 4,), float("nan"), device=DEV)      # a slab element no workgroup writes folds as NaN
         d.workspace, d.workspace_bytes = ws.data_ptr(), int(info.ws_bytes[i])
         wss.append(ws)
     host = (C.c_char * int(L.hrp_batch_table_bytes(nv.BATCH_WGRAD, n)))()
@@ -107,7 +107,7 @@ def test_eight_wave_program_alone_accumulates():
     nv.check(L.hrp_batch_prepare(nv.BATCH_WGRAD, arr, 2, None, C.byref(info)), "query")
     wss = []
     for i, d in enumerate(arr):
-        ws = torch.zeros(int(info.ws_bytes[i]) // 4 + 4, device=DEV)
+        ws = torch.full((int(info.ws_bytes[i]) // 4 + 4,), float("nan"), device=DEV)      # a slab element no workgroup writes folds as NaN
         d.workspace, d.workspace_bytes = ws.data_ptr(), int(info.ws_bytes[i])
         wss.append(ws)
     host = (C.c_char * int(L.hrp_batch_table_bytes(nv.BATCH_WGRAD, 2)))()
@@ -140,7 +140,7 @@ def test_eight_wave_program_fp32x3_pointwise_layers():
     nv.check(L.hrp_batch_prepare(nv.BATCH_WGRAD, arr, n, None, C.byref(info)), "query")
     wss = []
     for i, d in enumerate(arr):
-        ws = torch.zeros(int(info.ws_bytes[i]) // 4 + 4, device=DEV)
+        ws = torch.full((int(info.ws_bytes[i]) // 4 + 4,), float("nan"), device=DEV)      # a slab element no workgroup writes folds as NaN
         d.workspace, d.workspace_bytes = ws.data_ptr(), int(info.ws_bytes[i])
         wss.append(ws)
     host = (C.c_char * int(L.hrp_batch_table_bytes(nv.BATCH_WGRAD, n)))()
@@ -176,7 +176,7 @@ def test_eight_wave_program_stride_2_layers(phase, x3):
     nv.check(L.hrp_batch_prepare(nv.BATCH_WGRAD, arr, n, None, C.byref(info)), "query")
     wss = []
     for i, d in enumerate(arr):
-        ws = torch.zeros(int(info.ws_bytes[i]) // 4 + 4, device=DEV)
+        ws = torch.full((int(info.ws_bytes[i]) // 4 + 4,), float("nan"), device=DEV)      # a slab element no workgroup writes folds as NaN
         d.workspace, d.workspace_bytes = ws.data_ptr(), int(info.ws_bytes[i])
         wss.append(ws)
     host = (C.c_char * int(L.hrp_batch_table_bytes(nv.BATCH_WGRAD, n)))()

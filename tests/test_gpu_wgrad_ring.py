@@ -87,7 +87,7 @@ def _run(nv, name, phase, accumulate, fill):
     info = nv.BatchInfo()
     nv.check(L.hrp_batch_prepare(nv.BATCH_WGRAD, arr, n, None, C.byref(info)), "query")
     for i, d in enumerate(arr):
-        ws = torch.zeros(int(info.ws_bytes[i]) // 4 + 4, device=DEV)
+        ws = torch.full((int(info.ws_bytes[i]) // 4 + 4,), float("nan"), device=DEV)      # a slab element no workgroup writes folds as NaN
         d.workspace, d.workspace_bytes = ws.data_ptr(), int(info.ws_bytes[i])
         wss.append(ws)
     host = (C.c_char * int(L.hrp_batch_table_bytes(nv.BATCH_WGRAD, n)))()
