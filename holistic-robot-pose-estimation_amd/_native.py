@@ -299,6 +299,8 @@ class JpegSegment(C.Structure):   # hrp_jpeg_segment
 TRACK_NO_ESTIMATE, TRACK_BAD_BOX, TRACK_LOST_OUT = 1, 2, 4             # HRP_TRACK_*
 TRACK_BBOX_EXTENDED, TRACK_BBOX_ORIGIN, TRACK_BBOX_STRICT = 0, 1, 2    # HRP_TRACK_BBOX_*
 TRACK_MAX_KP, TRACK_MAX_SIZE = 32, 4096
+SEED_SKIPPED, SEED_TAKEN, SEED_REFUSED = 1, 2, 4                        # HRP_SEED_*
+KP_STRIP_ROWS = 1                                                       # HRP_KP_STRIP_ROWS: input rows per workgroup of hrp_kp_readout_fwd
 
 
 class TrackGeom(C.Structure):     # hrp_track_geom
@@ -403,6 +405,10 @@ PROTOTYPES = {
     "hrp_jpeg_sync_scratch_bytes": [_Z, _I, _I],      # returns size_t (set in lib())
     "hrp_track_prepare": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P],
     "hrp_track_update": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "hrp_track_seed": [_P, _I, _I, C.POINTER(C.c_double), _P, _I, _I, _F, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
+    "hrp_kp_readout_pack": [_P, _I, _I, _P, _I, _P],
+    "hrp_kp_readout_ws": [_I, _I],                    # returns int64 (set in lib())
+    "hrp_kp_readout_fwd": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _L, _P],
 }
 
 _lib = None
@@ -458,6 +464,7 @@ def lib():
         L.hrp_block_table_bytes.restype = C.c_int64
         L.hrp_block_table_bytes.argtypes = []
         L.hrp_jpeg_sync_scratch_bytes.restype = C.c_size_t
+        L.hrp_kp_readout_ws.restype = C.c_int64
         _lib = L
     return _lib
 

@@ -5,7 +5,8 @@
 //
 // hrp_track_prepare is ONE launch: at B = 1 .. 16 the work is latency-bound, so every workgroup derives its stream's record
 // itself (lane 0, a few hundred float64 operations, into LDS) instead of waiting for a geometry launch, and then walks its share
-// of the pixels of both views.  hrp_track_update is one launch with one lane per stream.
+// of the pixels of both views.  hrp_track_update and hrp_track_seed (acquisition from a detector's key-points) are one launch with
+// one lane per stream.
 #include "hrp_common.h"
 #include "track_core.h"
 
@@ -71,6 +72,22 @@ __global__ void __launch_bounds__(UPDATE_THREADS) track_update_kernel(const floa
   if (!have) status[b] |= HRP_TRACK_LOST_OUT;
 }
 
+__global__ void __launch_bounds__(UPDATE_THREADS) track_seed_kernel(const float* __restrict__ det_kp, int B, int nkp, double inv_sx,
+                                                                    double inv_sy, const float* __restrict__ mask, int hm, int wm,
+                                                                    float min_prob, const float* __restrict__ ms, float min_peak,
+                                                                    int min_inside, int force, int W, int H,
+                                                                    double* __restrict__ state_kp2d, int32_t* __restrict__ state_have,
+                                                                    int32_t* __restrict__ seed_status) {
+  const int b = blockIdx.x * UPDATE_THREADS + threadIdx.x;
+  if (b >= B) return;
+  int32_t have = state_have[b];
+  const int st = track::track_seed(det_kp + (int64_t)b * nkp * 2, nkp, inv_sx, inv_sy, mask ? mask + (int64_t)b * hm * wm : nullptr, hm,
+                                   wm, min_prob, ms ? ms + (int64_t)b * nkp * 2 : nullptr, min_peak, min_inside, force, W, H,
+                                   state_kp2d + (int64_t)b * nkp * 2, have);
+  if (st == HRP_SEED_TAKEN) state_have[b] = have;
+  seed_status[b] = st;
+}
+
 bool size_ok(int v) { return v >= 1 && v <= HRP_TRACK_MAX_SIZE; }
 
 }  // namespace
@@ -107,4 +124,20 @@ extern "C" int hrp_track_update(const float* xyz_fk, const float* K_original, in
   hipLaunchKernelGGL(track_update_kernel, dim3(cdiv(B, UPDATE_THREADS)), dim3(UPDATE_THREADS), 0, (hipStream_t)stream, xyz_fk,
                      K_original, B, nkp, W, H, min_inside, state_kp2d, state_have, kp2d_out, status);
   return check_launch("track_update");
+}
+
+extern "C" int hrp_track_seed(const float* det_kp, int B, int nkp, const double* inv_scale, const float* mask, int hm, int wm,
+                              float min_prob, const float* ms, float min_peak, int min_inside, int force, int W, int H,
+                              double* state_kp2d, int32_t* state_have, int32_t* seed_status, void* stream) {
+  HRP_REQUIRE(det_kp && inv_scale && state_kp2d && state_have && seed_status, "track_seed: null pointer");
+  HRP_REQUIRE(B >= 1 && B <= 65535, "track_seed: %d streams", B);
+  HRP_REQUIRE(nkp >= 1 && nkp <= HRP_TRACK_MAX_KP, "track_seed: %d key-points, want 1 .. %d", nkp, HRP_TRACK_MAX_KP);
+  HRP_REQUIRE(size_ok(H) && size_ok(W), "track_seed: frame %d x %d, want 1 .. %d", H, W, HRP_TRACK_MAX_SIZE);
+  HRP_REQUIRE(!mask || (size_ok(hm) && size_ok(wm)), "track_seed: mask %d x %d, want 1 .. %d", hm, wm, HRP_TRACK_MAX_SIZE);
+  HRP_REQUIRE(track::finite64(inv_scale[0]) && track::finite64(inv_scale[1]) && inv_scale[0] > 0.0 && inv_scale[1] > 0.0,
+              "track_seed: inv_scale must be finite and positive");
+  hipLaunchKernelGGL(track_seed_kernel, dim3(cdiv(B, UPDATE_THREADS)), dim3(UPDATE_THREADS), 0, (hipStream_t)stream, det_kp, B, nkp,
+                     inv_scale[0], inv_scale[1], mask, hm, wm, min_prob, ms, min_peak, min_inside, force, W, H, state_kp2d, state_have,
+                     seed_status);
+  return check_launch("track_seed");
 }

@@ -333,4 +333,43 @@ TRK_HD int track_update(const float* xyz, int nkp, const float* K_original, int 
   return (good && inside >= min_inside) ? 1 : 0;
 }
 
+// ---- acquisition: the estimate from a detector's key-points -------------------------------------------------------------------
+// det [nkp][2] fp32 in DETECTOR pixels (x, y), inv_sx / inv_sy frame pixels per detector pixel; mask [hm][wm] fp32 at detector
+// resolution or null; ms [nkp][2] (max logit, sum exp) or null.  have != 0 without force: HRP_SEED_SKIPPED, nothing is written.
+// Otherwise u = (double)det * inv_scale; a key-point counts when it is finite, lies in [0, W) x [0, H), the mask at its truncated
+// detector pixel is >= min_prob and its peak probability 1 / sum-exp is >= min_peak.  Every key-point finite and at least
+// min_inside counting: all nkp points are written to state [nkp][2], have = 1, HRP_SEED_TAKEN; else nothing is written,
+// HRP_SEED_REFUSED.  The mask index is formed only from values already tested against [0, wm) x [0, hm).
+TRK_HD int track_seed(const float* det, int nkp, double inv_sx, double inv_sy, const float* mask, int hm, int wm, float min_prob,
+                      const float* ms, float min_peak, int min_inside, int force, int W, int H, double* state, int32_t& have) {
+  if (have && !force) return HRP_SEED_SKIPPED;
+  bool finite = finite64(inv_sx) && finite64(inv_sy);
+  int counted = 0;
+  for (int i = 0; i < nkp; ++i) {
+    const float dx = det[2 * i], dy = det[2 * i + 1];
+    const double u = (double)dx * inv_sx, v = (double)dy * inv_sy;
+    if (!finite32(dx) || !finite32(dy) || !finite64(u) || !finite64(v)) {
+      finite = false;
+      continue;
+    }
+    bool ok = u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H;
+    if (ok && mask) {
+      ok = dx >= 0.f && dx < (float)wm && dy >= 0.f && dy < (float)hm;       // tested first: the casts below are in range
+      if (ok) {
+        const int mx = (int)dx, my = (int)dy;
+        ok = mx >= 0 && mx < wm && my >= 0 && my < hm && mask[(int64_t)my * wm + mx] >= min_prob;
+      }
+    }
+    if (ok && ms) ok = fdiv(1.f, ms[2 * i + 1]) >= min_peak;                 // (NaN compares false)
+    if (ok) ++counted;
+  }
+  if (!finite || counted < min_inside) return HRP_SEED_REFUSED;
+  for (int i = 0; i < nkp; ++i) {
+    state[2 * i] = (double)det[2 * i] * inv_sx;
+    state[2 * i + 1] = (double)det[2 * i + 1] * inv_sy;
+  }
+  have = 1;
+  return HRP_SEED_TAKEN;
+}
+
 }  // namespace track

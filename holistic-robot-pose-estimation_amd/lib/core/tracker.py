@@ -13,7 +13,9 @@ lib/utils/geometries.py:360-395) and its step derives ``k_values`` from the anno
 Nothing crosses PCIe except the frame, nothing here synchronises or reads a device value, every buffer is owned by the tracker and
 reused, so ``prepare`` and ``update`` can be captured in a graph.  A stream without a usable estimate (none yet, a box the loader
 would refuse, a prediction behind the camera or outside the frame) takes the whole frame and says so in ``status``; it recovers
-as soon as a prediction is usable again.  ``process_truncation`` is not part of the tracker: it crops inside the frame.  There is
+as soon as a prediction is usable again, or - the networks were trained on tight crops - at the next ACQUISITION: ``acquire`` runs a
+full-frame detector (CtRNet's ``seg_mask_inference.detect``) and one launch (``hrp_track_seed``) makes its key-points the estimate of
+the streams that have none; ``step`` schedules it every ``acquire_every`` frames.  ``process_truncation`` is not part of the tracker: it crops inside the frame.  There is
 no CPU path: CPU tensors raise HrpError."""
 import ctypes as C
 from collections import namedtuple
@@ -31,12 +33,23 @@ class PoseTracker:
 
     def __init__(self, model, robot, K_original, frame_hw, streams=1, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256),
                  extend_ratio=(0.2, 0.13), use_origin_bbox=False, use_extended_bbox=True, reference_keypoint_id=3, min_inside=1,
-                 device=None):
+                 device=None, detector=None, detector_scale=0.5, acquire_every=0):
         """model: a callable with RootNetwithRegInt.forward's signature returning its tuple (xyz_fk last); a module is put in
         eval().  robot: its ``nkp`` (or ``link_names``) gives the number of key-points.  K_original: [3, 3] or [streams, 3, 3].
         frame_hw: (H, W) of every frame.  The bbox options select the box and K of ``k_values`` as prepare_batch does
         (use_extended_bbox first, then use_origin_bbox, else the strict box).  reference_keypoint_id is the model's root key-point,
-        kept for the caller.  min_inside: how many predicted key-points must lie in the frame for the estimate to be used."""
+        kept for the caller.  min_inside: how many predicted key-points must lie in the frame for the estimate to be used.
+        detector: a callable uint8 [B, 3, H, W] -> (key-points [B, nkp, 2] fp32 in ITS pixels, foreground probability [B, 1, h, w] /
+        [B, h, w] or None, ms [B, nkp, 2] or None), e.g. ``seg_mask_inference.detect``; detector_scale: detector pixels per frame
+        pixel (a number or (x, y); seg_mask_inference's ``scale``); acquire_every: ``step`` runs ``acquire`` on every
+        acquire_every-th frame (0: never)."""
+        ds = tuple(detector_scale) if isinstance(detector_scale, (tuple, list)) else (detector_scale, detector_scale)
+        if len(ds) != 2 or not all(np.isfinite(float(v)) and float(v) > 0 for v in ds):
+            raise nv.HrpError(f"PoseTracker: detector_scale {detector_scale!r}, want one or two positive numbers")
+        if int(acquire_every) < 0 or (int(acquire_every) > 0 and detector is None):
+            raise nv.HrpError(f"PoseTracker: acquire_every {acquire_every!r} (>= 0, and > 0 only with a detector)")
+        self.detector, self.acquire_every, self._frame = detector, int(acquire_every), 0
+        self._inv_scale = (C.c_double * 2)(1.0 / float(ds[0]), 1.0 / float(ds[1]))       # frame pixels per detector pixel
         device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if device.type != "cuda":
             raise nv.HrpError(f"PoseTracker: {device} is not a GPU (there is no CPU path)")
@@ -71,14 +84,17 @@ class PoseTracker:
         self._geom_status = self.geom.view(torch.int32)[:, 0]
         self.kp2d_original = new(B, self.nkp, 2, dt=torch.float32)
         self.jpeg_status = None
+        self.seed_status = new(B, dt=torch.int32)
 
     def reset(self, kp2d=None, streams=None):
         """Seed the estimate: kp2d [B, nkp, 2] in original-image pixels (float64 is kept bit for bit), or None for no estimate.
-        streams: the indices it applies to (kp2d then has one row per index); the other streams keep their state."""
+        streams: the indices it applies to (kp2d then has one row per index); the other streams keep their state.  Dropping an
+        estimate also restarts the host frame count of ``acquire_every``: the next ``step`` runs the detector."""
         idx = torch.arange(self.B) if streams is None else torch.as_tensor(list(streams), dtype=torch.int64)
         idx = idx.to(self.device)
         if kp2d is None:
             self.have.index_fill_(0, idx, 0)
+            self._frame = 0                  # the next step is a scheduled detection again (acquire_every)
             return
         kp = torch.as_tensor(kp2d, dtype=torch.float64).to(self.device)
         if tuple(kp.shape) != (idx.numel(), self.nkp, 2):
@@ -89,14 +105,54 @@ class PoseTracker:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def prepare(self, frames):
-        """frames: uint8 [B, H, W, 3] on the device.  Returns the model's inputs (tensors owned by the tracker, rewritten by the
-        next call): root_images / reg_images uint8 [B, 3, h, w], root_K / other_K [B, 3, 3], k_values [B], geom [B, 112] uint8
-        (hrp_track_geom records: crop box, canvas, boxes, status)."""
+    def _check_frames(self, frames):
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8:
             raise nv.HrpError("PoseTracker: frames must be a uint8 GPU tensor (there is no CPU path)")
         if tuple(frames.shape) != (self.B, self.H, self.W, 3):
             raise nv.HrpError(f"PoseTracker: frames {tuple(frames.shape)}, want {(self.B, self.H, self.W, 3)}")
+
+    def seed(self, det_kp, mask=None, ms=None, force=False, min_inside=None, min_prob=0.5, min_peak=0.0):
+        """One launch (``hrp_track_seed``): the detector's key-points [B, nkp, 2] fp32 (its pixels) become the estimate of the streams
+        that have none (force: of every stream).  A key-point counts when it is finite, lies in the frame, the mask [B, 1, h, w] /
+        [B, h, w] (if given) is >= min_prob at its detector pixel and its peak probability 1 / ms[..., 1] (if given) is >= min_peak;
+        a stream takes the detection when all its key-points are finite and at least min_inside (default: the tracker's) count.
+        Returns ``seed_status`` [B] int32 (_native.SEED_SKIPPED / SEED_TAKEN / SEED_REFUSED), the tracker's own buffer."""
+        def dev32(t, shapes, what):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise nv.HrpError(f"PoseTracker.seed: {what} must be a GPU tensor (there is no CPU path)")
+            if tuple(t.shape) not in shapes:
+                raise nv.HrpError(f"PoseTracker.seed: {what} {tuple(t.shape)}, want {shapes[0]}")
+            return t.detach().float().contiguous()
+        kp = dev32(det_kp, [(self.B, self.nkp, 2)], "key-points")
+        hm = wm = 0
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dim() not in (3, 4) or mask.shape[0] != self.B:
+                raise nv.HrpError(f"PoseTracker.seed: mask {tuple(mask.shape)}, want [B, 1, h, w] or [B, h, w]")
+            hm, wm = int(mask.shape[-2]), int(mask.shape[-1])
+            mask = dev32(mask, [(self.B, 1, hm, wm), (self.B, hm, wm)], "mask")
+        if ms is not None:
+            ms = dev32(ms, [(self.B, self.nkp, 2)], "ms")
+        nv.call("hrp_track_seed", kp.data_ptr(), self.B, self.nkp, self._inv_scale, None if mask is None else mask.data_ptr(), hm, wm,
+                float(min_prob), None if ms is None else ms.data_ptr(), float(min_peak),
+                self.min_inside if min_inside is None else int(min_inside), 1 if force else 0, self.W, self.H, self.kp2d.data_ptr(),
+                self.have.data_ptr(), self.seed_status.data_ptr(), self._stream())
+        return self.seed_status
+
+    def acquire(self, frames, force=False, min_inside=None, min_prob=0.5, min_peak=0.0):
+        """Run the detector on the frames (uint8 [B, H, W, 3] on the device) and seed the streams without an estimate from it
+        (``seed``).  Returns ``seed_status``; never synchronises.  The NHWC -> NCHW view the detector takes is a torch copy."""
+        if self.detector is None:
+            raise nv.HrpError("PoseTracker.acquire: the tracker was built without a detector")
+        self._check_frames(frames)
+        with torch.no_grad():
+            kp, mask, ms = self.detector(frames.permute(0, 3, 1, 2).contiguous())
+        return self.seed(kp, mask, ms, force=force, min_inside=min_inside, min_prob=min_prob, min_peak=min_peak)
+
+    def prepare(self, frames):
+        """frames: uint8 [B, H, W, 3] on the device.  Returns the model's inputs (tensors owned by the tracker, rewritten by the
+        next call): root_images / reg_images uint8 [B, 3, h, w], root_K / other_K [B, 3, 3], k_values [B], geom [B, 112] uint8
+        (hrp_track_geom records: crop box, canvas, boxes, status)."""
+        self._check_frames(frames)
         frames = frames.contiguous()
         nv.call("hrp_track_prepare", frames.data_ptr(), self.kp2d.data_ptr(), self.have.data_ptr(), self.K_original.data_ptr(), self.B,
                 self.H, self.W, self.nkp, self.root_images.data_ptr(), self.root_hw[0], self.root_hw[1],
@@ -132,9 +188,15 @@ class PoseTracker:
     def step(self, frames):
         """One frame per stream: prepare, the model, update.  frames: uint8 [B, H, W, 3] on the device, or a list of JPEG bytes.
         Returns TrackResult(pose, rot, trans, kp3d, kp2d_original, depth, status, k_values), device tensors; kp2d_original,
-        status and k_values are the tracker's own buffers."""
+        status and k_values are the tracker's own buffers.  With a detector and acquire_every = n > 0, every n-th frame (counted
+        on the host, the first included) runs ``acquire`` first: only streams without an estimate take the detection, so a lost
+        stream recovers at the next scheduled detection without a read-back.  Without, exactly prepare - model - update."""
         if isinstance(frames, (list, tuple)):
             frames = self.decode(frames)
+        if self.acquire_every > 0:
+            if self._frame % self.acquire_every == 0:
+                self.acquire(frames)
+            self._frame += 1
         p = self.prepare(frames)
         with torch.no_grad():
             out = tuple(self.model(p["reg_images"], p["root_images"], p["k_values"], p["other_K"]))

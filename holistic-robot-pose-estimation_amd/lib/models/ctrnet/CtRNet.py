@@ -1,12 +1,22 @@
-"""``CtRNet`` as far as the mask network uses it (reference lib/models/ctrnet/CtRNet.py:10-45, 102-111): the key-point /
-segmentation predictor behind a DataParallel-shaped wrapper (the reference's checkpoints carry the ``module.`` prefix) and
-``inference_batch_images_onlyseg``.  The BPnP pose solver (CtRNet.py:47-100: OpenCV on the host) is out of scope."""
+"""``CtRNet`` (reference lib/models/ctrnet/CtRNet.py:10-129): the key-point / segmentation predictor behind a DataParallel-shaped
+wrapper (the reference's checkpoints carry the ``module.`` prefix), the detection entry points and the pose from them:
+
+* ``inference_batch_images_onlyseg`` (102-111), the mask network's call, unchanged;
+* ``inference_batch_images_seg_kp`` (91-100): key-points and foreground probability from one plan;
+* ``inference_batch_images`` / ``inference_single_image`` (49-89): the same, plus ``cTr`` from the GPU PnP solver (``BPnP_m3d`` /
+  ``BPnP``, lib/utils/BPnP.py, csrc/pnp.hip - the reference calls OpenCV on the host);
+* ``cTr_to_pose_matrix`` (114-124), ``to_valid_R_batch`` (126-129).
+
+Not built: ``render_single_robot_mask`` and ``train_on_batch`` (131-194; training the key-point network is out of scope)."""
 import os
 import sys
 
 import numpy as np
 import torch
 
+from hrpe_amd import _native as nv
+from hrpe_amd.lib.utils.BPnP import BPnP, BPnP_m3d
+from hrpe_amd.lib.utils.geometries import angle_axis_to_rotation_matrix
 from .keypoint_seg_resnet import KeyPointSegNet
 
 
@@ -48,7 +58,57 @@ class CtRNet(torch.nn.Module):
         _, segmentation = self.keypoint_seg_predictor(img)
         return torch.sigmoid(segmentation)
 
-    def inference_single_image(self, img, joint_angles):
-        raise NotImplementedError("CtRNet's BPnP pose solver (OpenCV on the host) is outside this library's path")
+    def _seg_kp(self, img):
+        return self.keypoint_seg_predictor(img, keypoints=True)
 
-    inference_batch_images = inference_batch_images_seg_kp = inference_single_image
+    def _points_3d(self, joint_angles, points_3d, batch):
+        """The 3-D key-points the 2-D detections are paired with.  Default: ``self.robot.get_keypoints_only_fk(joint_angles)`` of a
+        ``URDFRobot`` the CALLER assigns to ``self.robot`` (the reference never assigns ``self.robot`` either, and its
+        ``get_joint_RT`` comes from roboticstoolbox, which is not in the reference tree); scripts/test.py:121-122 pairs the same FK
+        key-points with ``BPnP_m3d``.  UNPINNED: whether the link origins CtRNet's checkpoints were trained on coincide with the
+        DREAM key-point offsets of ``URDFRobot`` is not verified by anything in either tree; pass ``points_3d`` to choose."""
+        if points_3d is not None:
+            return points_3d
+        robot = getattr(self, "robot", None)
+        if robot is None:
+            raise nv.HrpError("CtRNet: the pose needs 3-D key-points: assign a URDFRobot to `robot` (its get_keypoints_only_fk(joint_angles) "
+                              "is used) or pass `points_3d`")
+        q = torch.as_tensor(joint_angles, dtype=torch.float32, device=self.K.device)
+        pts = robot.get_keypoints_only_fk(q if batch else q[None])
+        return pts if batch else pts[0]
+
+    def inference_batch_images_seg_kp(self, img):
+        """img [B, 3, H, W] (normalised) -> (points_2d [B, k, 2] in pixels, foreground probability [B, 1, H, W]) (CtRNet.py:91-100)"""
+        points_2d, segmentation = self._seg_kp(img)
+        return points_2d, torch.sigmoid(segmentation)
+
+    def inference_batch_images(self, img, joint_angles, points_3d=None):
+        """img [B, 3, H, W], joint_angles [B, dof] -> (cTr [B, 6] angle-axis + translation from BPnP_m3d, points_2d [B, k, 2],
+        foreground probability) (CtRNet.py:68-89).  points_3d [B, k, 3]: see ``_points_3d``."""
+        points_2d, segmentation = self._seg_kp(img)
+        pts = self._points_3d(joint_angles, points_3d, True)
+        cTr = BPnP_m3d.apply(points_2d, pts.to(points_2d.device), self.K)
+        return cTr, points_2d, torch.sigmoid(segmentation)
+
+    def inference_single_image(self, img, joint_angles, points_3d=None):
+        """img [3, H, W], joint_angles [dof] -> (cTr [1, 6] from BPnP, points_2d [1, k, 2], foreground probability [1, 1, H, W])
+        (CtRNet.py:49-66).  points_3d [k, 3]: see ``_points_3d``."""
+        points_2d, segmentation = self._seg_kp(img[None])
+        pts = self._points_3d(joint_angles, points_3d, False)
+        cTr = BPnP.apply(points_2d, pts.to(points_2d.device), self.K)
+        return cTr, points_2d, torch.sigmoid(segmentation)
+
+    def cTr_to_pose_matrix(self, cTr):
+        """cTr [B, 6] -> pose matrix [B, 4, 4] (CtRNet.py:114-124) with BPnP.py's own axis-angle conversion
+        (lib/utils/geometries.angle_axis_to_rotation_matrix, the one tests/golden/golden_pnp.npz pins)."""
+        bs = cTr.shape[0]
+        pose = torch.zeros((bs, 4, 4), device=cTr.device, dtype=cTr.dtype)
+        pose[:, :3, :3] = angle_axis_to_rotation_matrix(cTr[:, :3].reshape(bs, 3))[:, :3, :3]
+        pose[:, :3, 3] = cTr[:, 3:]
+        pose[:, 3, 3] = 1
+        return pose
+
+    def to_valid_R_batch(self, R):
+        """The nearest orthogonal matrices of a batch of 3 x 3 matrices (CtRNet.py:126-129): U V^T of the SVD."""
+        U, _, Vh = torch.linalg.svd(R)
+        return torch.bmm(U, Vh)

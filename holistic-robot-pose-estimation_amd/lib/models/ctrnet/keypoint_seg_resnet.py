@@ -3,9 +3,13 @@ one-class head, executed as a static plan of HIP launches.  Same class name and 
 (``backbone.0.*`` = the dilated ResNet-50, ``classifer.0.*`` = torchvision's DeepLabHead - the reference's spelling -,
 ``read_out.kps_score_lowres.*``), so the authors' ``models/panda_segmentation/*.pth`` files load unchanged.
 
-Only the SEGMENTATION branch is executed: the mask network's one caller, ``inference_batch_images_onlyseg`` (CtRNet.py:102-111),
-discards the key-points; the key-point branch exists for CtRNet's BPnP pose solver (OpenCV on the host, SURVEY 2 out of scope).
-``forward`` therefore returns ``(None, segout)``.
+Both branches are executed.  The SEGMENTATION branch is what the mask network's caller, ``inference_batch_images_onlyseg``
+(CtRNet.py:102-111), uses, and what ``forward`` returns by default: ``(None, segout)``.  With ``with_keypoints = True`` (off by
+default; the switch takes part in the plan selection) or ``forward(img, keypoints=True)`` it returns
+``(keypoints [B, k, 2], segout)`` from ONE plan, as the reference's forward does (lines 131-149): the key-point branch is
+``KeypointUpSample`` + ``SpatialSoftArgmax`` (lines 29-33, 75-100, 137-143) as one HIP launch pair that keeps the
+[B, k, H/4, W/4] heat-map in fp32 registers (PlanBuilder.kp_readout, csrc/kp_readout.hip), so a bf16 plan never rounds the logits
+the soft-argmax exponentiates.  The segmentation output is bit for bit the same either way.
 
 Architecture restated from torchvision 0.14 (models/segmentation/deeplabv3.py, models/resnet.py): ResNet-50 v1.5 with
 ``replace_stride_with_dilation=[False, True, True]`` (layer3 / layer4 keep 1/8 resolution with dilation 2 / 4), ASPP with rates
@@ -112,8 +116,9 @@ class _ASPP(PlannedModule):
 
 
 class KeypointUpSample(PlannedModule):
-    """Parameter holder of the key-point read-out (keypoint_seg_resnet.py:11-33: ConvTranspose2d(2048, k, 4, stride 2, padding 1)
-    with bias).  Not executed (module docstring); present so that the reference's checkpoints load with strict keys."""
+    """The key-point read-out (keypoint_seg_resnet.py:11-33: ConvTranspose2d(2048, k, 4, stride 2, padding 1) with bias; the
+    interpolate(scale_factor=1) behind it is the identity), executed together with the spatial soft-argmax that consumes its
+    heat-map (``emit``).  Same parameter names as the reference, so its checkpoints load with strict keys."""
 
     def __init__(self, in_channels, num_keypoints):
         super().__init__()
@@ -121,6 +126,11 @@ class KeypointUpSample(PlannedModule):
         self.kps_score_lowres.weight = nn.Parameter(torch.zeros(in_channels, num_keypoints, 4, 4))
         self.kps_score_lowres.bias = nn.Parameter(torch.zeros(num_keypoints))
         nn.init.kaiming_normal_(self.kps_score_lowres.weight, mode="fan_out", nonlinearity="relu")
+        self.up_scale, self.out_channels = 1, num_keypoints
+
+    def emit(self, pb, feat, lim, size):
+        """feat [N, H, W, Cin] -> (key-points [N, 2k] in pixels of size = (width, height), ms [N, 2k]); lines 137-143."""
+        return pb.kp_readout(feat, self.kps_score_lowres.weight, self.kps_score_lowres.bias, lim, size)
 
 
 class KeyPointSegNet(PlannedModule):
@@ -128,30 +138,51 @@ class KeyPointSegNet(PlannedModule):
         super().__init__()
         self.args, self.lim = args, lim
         self.device = "cuda" if use_gpu else "cpu"
+        self.with_keypoints = False          # forward's default; takes part in the plan selection (PlannedModule._select_plans)
         self.backbone = nn.Sequential(_DilatedResNet50())
         self.read_out = KeypointUpSample(2048, args.n_kp)
         # torchvision DeepLabHead = Sequential(ASPP, Conv2d 3x3, BatchNorm2d, ReLU, Conv2d 1x1 -> one class (keypoint_seg_resnet.py:119))
         self.classifer = nn.Sequential(nn.Sequential(_ASPP(), Conv2d(256, 256, 3, bias=False), BatchNorm2d(256), nn.Identity(),
                                                      Conv2d(256, 1, 1, bias=True)))
 
-    def emit_logits(self, pb, xs):
-        """xs: normalised image, space-to-depth -> logits at 1/8 resolution [N, H/8, W/8, 1]"""
-        feat = self.backbone[0].emit(pb, xs)
+    def emit_features(self, pb, xs):
+        """xs: normalised image, space-to-depth -> layer4 features [N, H/8, W/8, 2048]"""
+        return self.backbone[0].emit(pb, xs)
+
+    def emit_head(self, pb, feat):
+        """layer4 features -> logits at 1/8 resolution [N, H/8, W/8, 1]"""
         head = self.classifer[0]
         y = head[0].emit(pb, feat)
         y = pb.act([conv_bn(pb, y, head[1], head[2])], relu=True)
         return head[4].emit(pb, y)
+
+    def emit_keypoints(self, pb, feat):
+        """layer4 features -> (key-points [N, 2k] in pixels of (args.width, args.height), ms [N, 2k])"""
+        return self.read_out.emit(pb, feat, self.lim, (self.args.width, self.args.height))
+
+    def emit_logits(self, pb, xs):
+        """xs: normalised image, space-to-depth -> logits at 1/8 resolution [N, H/8, W/8, 1]"""
+        return self.emit_head(pb, self.emit_features(pb, xs))
 
     def _build(self, pb, img):
         if pb.plan.need_grad or pb.plan.training:
             raise NotImplementedError("KeyPointSegNet is an inference network here (eval(), no gradients): the reference never trains it")
         N, Cc, H, W = img.shape
         t = pb.image_input_s2d("img", N, Cc, H, W, u8=False)
-        logits = self.emit_logits(pb, t)
+        feat = self.emit_features(pb, t)
+        logits = self.emit_head(pb, feat)
         holder = pb.bilinear_nchw_output(logits, H, W)              # F.interpolate(x, size=input_shape, mode='bilinear', align_corners=False)
         holder["handle"] = logits
-        return ["img"], [("nchw", holder, None)], {"img": t}
+        outs = [("nchw", holder, None)]
+        if self._plan_mode:
+            kp, _ = self.emit_keypoints(pb, feat)
+            outs.append(("vec", kp, (N, self.args.n_kp, 2)))
+        return ["img"], outs, {"img": t}
 
-    def forward(self, img):
-        """-> (None, segout [B, 1, H, W]); see the module docstring for the key-points."""
-        return None, self._run(img)[0]
+    def forward(self, img, keypoints=None):
+        """-> (None, segout [B, 1, H, W]), or with key-points (keypoints [B, k, 2] as (x, y) in pixels of
+        (args.width, args.height), segout).  keypoints: True / False for this call, None for ``self.with_keypoints``."""
+        on = bool(self.with_keypoints if keypoints is None else keypoints)
+        self._select_plans(on)
+        r = self._run(img)
+        return (r[1] if on else None), r[0]

@@ -5,6 +5,7 @@ The reference moves every image to the host, resizes it with PIL, normalises it 
 and runs CtRNet's DeepLabv3-ResNet50.  Here the whole call is ONE static plan on the device: hrp_pil_resize_normalize (bit-exact
 with PIL.Image.resize on the bytes) -> the network (KeyPointSegNet.emit_logits) -> bilinear up-sampling + sigmoid in one launch.
 Same constructor, attribute names (``net``, ``args``) and state-dict keys (``net.keypoint_seg_predictor.module.*``).
+``detect`` adds the key-point head to the same plan (PlanBuilder.kp_readout): key-points, mask and peak statistics of one frame.
 PARITY: the resize is pinned against Pillow itself; the network is parity-unpinned (keypoint_seg_resnet.py docstring)."""
 import argparse
 
@@ -52,11 +53,30 @@ class seg_mask_inference(PlannedModule):
         assert Cc == 3
         t = pb.pil_resize_input("img", N, H, W, self.args.scale, MEAN, STD)
         seg = self.net.keypoint_seg_predictor.module
-        logits = seg.emit_logits(pb, t)
+        feat = seg.emit_features(pb, t)
+        logits = seg.emit_head(pb, feat)
         Ho, Wo = int(H * self.args.scale), int(W * self.args.scale)
         holder = pb.bilinear_nchw_output(logits, Ho, Wo, sigmoid=True)
         holder["handle"] = logits
-        return ["img"], [("nchw", holder, None)], {"img": t}
+        outs = [("nchw", holder, None)]
+        if self._plan_mode:
+            k = self.args.n_kp
+            # (the soft-argmax scales by args.width // 2, args.height // 2 as the reference does: the pixels of the resized image)
+            kp, ms = seg.emit_keypoints(pb, feat)
+            outs += [("vec", kp, (N, k, 2)), ("vec", ms, (N, k, 2))]
+        return ["img"], outs, {"img": t}
+
+    def _run_mode(self, detect, img_tensor):
+        self._select_plans(detect)           # the two entry points have plans of their own
+        return self._run(img_tensor)
 
     def forward(self, img_tensor):
-        return self._run(img_tensor)[0]
+        return self._run_mode(False, img_tensor)[0]
+
+    def detect(self, img_tensor):
+        """Raw images [B, 3, H, W] with values 0 .. 255 (float32 or uint8) -> (key-points [B, k, 2] as (x, y) in pixels of the
+        RESIZED image, foreground probability [B, 1, h, w], ms [B, k, 2] = (maximum logit, sum exp(l - max)) of every key-point's
+        heat-map: 1 / ms[..., 1] is its peak probability).  One plan: the trunk runs once for both heads.  This is the detector
+        ``PoseTracker(detector=...)`` takes (with ``detector_scale = args.scale``)."""
+        prob, kp, ms = self._run_mode(True, img_tensor)
+        return kp, prob, ms

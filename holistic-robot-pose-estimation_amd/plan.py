@@ -580,6 +580,7 @@ class Plan:
         self.bwd_split, self.split_active = None, False
         self.bwd_cuts = None       # k cut positions of the backward list (PlannedModule.enable_split_backward(fracs=...))
         self.pre_pack = []         # ops run before the weight packing of every step (derived weight layouts)
+        self.tracked_params = []   # parameters that only pre_pack ops read (PlanBuilder.kp_readout): their versions count in params_dirty
         self.counters = {}         # build statistics (HRP_PLAN_STATS=1 prints them at finalize)
         self.wgrad_ws_bytes = {}   # lane -> scratch bytes shared by that lane's weight-gradient launches
         self.wgrad_ws = {}
@@ -910,7 +911,7 @@ class Plan:
     def params_dirty(self):
         # tensor versions catch torch-side updates (torch.optim, load_state_dict); PARAM_EPOCH the updates made through
         # raw pointers (FusedClipAdam.step, hrp_bn_running_update), which do not bump ._version
-        v = tuple(w.param._version for w in self.weight_list) + \
+        v = tuple(w.param._version for w in self.weight_list) + tuple(t._version for t in self.tracked_params) + \
             tuple(t._version for bn, _, _ in self.bn_fold.values() for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)) + \
             (PARAM_EPOCH,)
         if v != self._versions:

@@ -414,6 +414,38 @@ class HeadOps:
             self.bwd_stack.append(bw)
         return coord
 
+    def kp_readout(self, feat, weight, bias, lim, size):
+        """CtRNet's key-point read-out and spatial soft-argmax (keypoint_seg_resnet.py:29-33, 75-100, 137-143) in one launch pair:
+        NHWC feature [N, H, W, Cin] -> (key-points fp32 [N, 2k] dense, (x, y) per channel in pixels of `size` = (width, height);
+        ms fp32 [N, 2k] = (max logit, sum exp) per channel).  weight [Cin, k, 4, 4] / bias [k]: the ConvTranspose2d's parameters;
+        lim = [x0, x1, y0, y1] of the module.  The [N, k, 2H, 2W] heat-map never exists (csrc/kp_readout.hip): its logits stay fp32
+        whatever the plan's element type.  The packed weight is rebuilt by Plan.run_prep whenever the parameter changed
+        (load_state_dict, an optimizer).  Inference plans only."""
+        p = self.plan
+        if p.need_grad:
+            raise NotImplementedError("kp_readout: forward only (the key-point network is an inference network here; "
+                                      "CtRNet.train_on_batch is out of scope)")
+        feat.check_readable()
+        cin, k = int(weight.shape[0]), int(weight.shape[1])
+        if tuple(weight.shape[2:]) != (4, 4) or feat.C != cin or tuple(bias.shape) != (k,):
+            raise nv.HrpError(f"kp_readout: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} for a feature of {feat.C} channels")
+        if weight.dtype != torch.float32 or bias.dtype != torch.float32 or not weight.is_contiguous():
+            raise nv.HrpError("kp_readout: weight and bias must be contiguous fp32 tensors")
+        N, dt = feat.N, PL._cdt(p, feat.dtype)
+        packed = torch.zeros(16 * cin * 32, dtype=feat.dtype, device=p.device)
+        wsb = int(nv.lib().hrp_kp_readout_ws(N, feat.H))
+        ws = torch.zeros(max(wsb // 4, 4), dtype=torch.float32, device=p.device)
+        p.keep += [packed, ws]
+        p.tracked_params += [weight, bias]
+        p.pre_pack.append(lambda s: nv.call("hrp_kp_readout_pack", weight.data_ptr(), cin, k, packed.data_ptr(), dt, s))
+        kp = p.new(N, 1, 1, 2 * k, torch.float32, pitch=2 * k)
+        ms = p.new(N, 1, 1, 2 * k, torch.float32, pitch=2 * k)
+        lim0, lim2 = float(lim[0]), float(lim[2])
+        sx, sy = float(int(size[0]) // 2), float(int(size[1]) // 2)
+        p.fwd.append(lambda s: nv.call("hrp_kp_readout_fwd", feat.ptr(), dt, N, feat.H, feat.W, cin, feat.pitch, packed.data_ptr(),
+                                       bias.data_ptr(), k, lim0, lim2, sx, sy, kp.ptr(), ms.ptr(), ws.data_ptr(), wsb, s))
+        return kp, ms
+
     def rot6d_compose(self, a, b):
         """out = rotmat_to_rot6d(R(a) @ R(b)) on dense fp32 [N, 6] tensors (full_net.py:362)."""
         p = self.plan

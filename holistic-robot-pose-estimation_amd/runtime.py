@@ -206,6 +206,13 @@ class PlannedModule(nn.Module):
         object.__setattr__(self, "_compute_dtype", torch.float32)
         object.__setattr__(self, "_x3", False)
         object.__setattr__(self, "_accum", None)
+        object.__setattr__(self, "_plan_mode", None)
+
+    def _select_plans(self, mode):
+        """A plan has its outputs baked in.  A module whose OUTPUT SET depends on a switch (KeyPointSegNet with / without
+        key-points, seg_mask_inference.forward / .detect) names the value of the switch here before it runs: it is a component of
+        the plan key of ``_run``, and ``_build`` reads ``self._plan_mode``."""
+        object.__setattr__(self, "_plan_mode", mode)
 
     # compute dtype of the convolution trunk (heads stay fp32)
     def set_compute_dtype(self, dtype):
@@ -391,7 +398,7 @@ class PlannedModule(nn.Module):
         bn_eval = self._frozen_bn_signature()
         key = (tuple(tuple(t.shape) for t in tensors), self._compute_dtype, self.training, need_grad,
                tuple(bool(t.requires_grad) for t in tensors) if need_grad else (),
-               tuple(t.dtype == torch.uint8 for t in tensors), bn_eval, self._x3)
+               tuple(t.dtype == torch.uint8 for t in tensors), bn_eval, self._x3, self._plan_mode)
         runner = self._plans.pop(key, None)
         if runner is not None:
             self._plans[key] = runner        # most recently used last

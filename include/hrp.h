@@ -72,8 +72,11 @@
  *                             and the crop + bilinear resize of both views straight from the frame, in one launch
  *                                                     lib/dataset/dream.py:171-216, 287-394; roboutils.py:59-156, 224-257;
  *                                                     lib/utils/geometries.py:360-395; lib/core/function.py:43-48, 88-98
+ *   hrp_track_seed            tracker acquisition from a detector's key-points (CtRNet's KeyPointSegNet, hrp_kp_readout_fwd)
  *   hrp_track_update          the projection of the model's FK key-points into the original image, which becomes the estimate the
  *                             next frame is cropped from          lib/utils/geometries.py:100-115; lib/dataset/dream.py:171-216
+ *   hrp_kp_readout_fwd        CtRNet's key-point branch: ConvTranspose2d read-out + spatial soft-argmax, the heat-map kept in fp32
+ *                             registers                           lib/models/ctrnet/keypoint_seg_resnet.py:29-33, 75-100, 137-143
  */
 #ifndef HRP_H
 #define HRP_H
@@ -1159,6 +1162,42 @@ int hrp_track_prepare(const uint8_t* frames, const double* state_kp2d, const int
                       int bbox_mode, float* K_root, float* K_other, float* k_values, hrp_track_geom* geom, void* stream);
 int hrp_track_update(const float* xyz_fk, const float* K_original, int B, int nkp, int W, int H, int min_inside, double* state_kp2d,
                      int32_t* state_have, float* kp2d_out, int32_t* status, void* stream);
+
+/* Tracker acquisition: a detector's key-points become the estimate of the streams that have none (csrc/track_core.h track_seed,
+ * host and device code like track_geometry; tests/track_seed_host_check.cpp).  hrp_track_seed is one launch, one lane per stream.
+ *   det_kp [B, nkp, 2] fp32 in DETECTOR pixels (x, y); inv_scale: two host doubles, frame pixels per detector pixel (x, y);
+ *   mask [B, hm, wm] fp32 at detector resolution with min_prob, or NULL; ms [B, nkp, 2] (max logit, sum exp(l - max)) as
+ *   hrp_kp_readout_fwd / hrp_softargmax_flat_fwd report them, with min_peak, or NULL; state_kp2d [B, nkp, 2] float64,
+ *   state_have [B] int32: the tracker's state; seed_status [B] int32: output.
+ * Per stream: have == 1 and force == 0 leave the state untouched (HRP_SEED_SKIPPED).  Otherwise u = (double)det_kp * inv_scale; a
+ * key-point COUNTS when it is finite, lies in [0, W) x [0, H), (with a mask) the mask at the truncated detector pixel is >= min_prob
+ * and (with ms) the peak probability 1 / sum-exp is >= min_peak.  If every key-point is finite and at least min_inside count, all
+ * nkp points go into the state, have = 1 (HRP_SEED_TAKEN); otherwise the state is untouched (HRP_SEED_REFUSED).  Every value is
+ * range-checked before every float -> int conversion.  No host synchronisation, caller-owned buffers: graph-capturable. */
+enum { HRP_SEED_SKIPPED = 1, HRP_SEED_TAKEN = 2, HRP_SEED_REFUSED = 4 };
+int hrp_track_seed(const float* det_kp, int B, int nkp, const double* inv_scale, const float* mask, int hm, int wm, float min_prob,
+                   const float* ms, float min_peak, int min_inside, int force, int W, int H, double* state_kp2d, int32_t* state_have,
+                   int32_t* seed_status, void* stream);
+
+/* CtRNet key-point read-out and spatial soft-argmax, forward only (csrc/kp_readout.hip; reference
+ * lib/models/ctrnet/keypoint_seg_resnet.py:29-33 KeypointUpSample.forward, 75-100 SpatialSoftArgmax.forward, 137-143):
+ *   heat = conv_transpose2d(x, w, b, stride 2, padding 1) [B, k, 2 Hin, 2 Win]; p = softmax over the positions of each (b, c);
+ *   kp[b, c] = (sum p xc - lim0, sum p yc - lim2) * (scale_x, scale_y), xc = linspace(-1, 1, 2 Win), yc = linspace(-1, 1, 2 Hin) in
+ *   fp32 as torch computes them; order (x, y).  The logits are fp32 accumulators of the matrix cores (mfma_f32_32x32x16_bf16 for
+ *   HRP_BF16 features, mfma_f32_32x32x2f32 for HRP_F32 and HRP_F32X3) and are never stored or rounded below fp32; partial sums are
+ *   combined in a fixed order, so the result is bit-reproducible from run to run.
+ * hrp_kp_readout_pack: weight [Cin, k, 4, 4] fp32 (nn.ConvTranspose2d's layout) -> the kernel's operand layout
+ *   [parity 4][tap 4][Cin / V][32][V] in the element type of `dtype` (V = 8 bf16 / 4 fp32): 16 * Cin * 32 elements.
+ * hrp_kp_readout_ws: bytes of the workspace (one softmax partial per (b, row strip of HRP_KP_STRIP_ROWS input rows, channel)).
+ * hrp_kp_readout_fwd: x [B, Hin, Win, pitch] NHWC in `dtype`, 16-byte aligned, pitch a multiple of V; bias [k] fp32;
+ *   kp [B, k, 2] fp32; ms [B, k, 2] = (maximum logit, sum exp(l - max)), so 1 / ms[..., 1] is the peak probability, or NULL.
+ * Refused (HRP_ERR_ARG): Cin not a multiple of 32, k outside 1 .. HRP_TRACK_MAX_KP, empty maps, null pointers. */
+#define HRP_KP_STRIP_ROWS 1
+int hrp_kp_readout_pack(const float* weight, int Cin, int k, void* packed, int dtype, void* stream);
+int64_t hrp_kp_readout_ws(int B, int Hin);
+int hrp_kp_readout_fwd(const void* x, int dtype, int B, int Hin, int Win, int Cin, int pitch, const void* packed, const float* bias,
+                       int k, float lim0, float lim2, float scale_x, float scale_y, float* kp, float* ms, void* ws, int64_t ws_bytes,
+                       void* stream);
 
 #ifdef __cplusplus
 }

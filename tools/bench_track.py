@@ -7,8 +7,11 @@
     that consumes the pose sees) and frames per second with the synchronise only at the end of the window.
 (c) the same loop written with the public pieces that existed before the tracker: read ``xyz_fk`` back, the loader's geometry in
     numpy per stream (get_bbox, _resize_geometry, _view), descriptor_table, upload, pixel_launches, compute_k_values, the model.
-Also: whether the model's forward synchronises (torch's sync debug mode around one call).  Prints one JSON line per B.
-Run on the GPU box: ``python tools/bench_track.py``."""
+(d) acquisition at B = 1, 4: ``PoseTracker.acquire`` (CtRNet's ``seg_mask_inference.detect`` in bf16 on the full frame + the seed
+    launch), the key-point read-out launch pair alone on the detector's 30 x 40 x 2048 feature, and ``step`` with
+    ``acquire_every=30``.  Nothing is gated on speed.
+Also: whether the model's forward synchronises (torch's sync debug mode around one call).  Prints one JSON line per B and row.
+Run on the GPU box: ``python tools/bench_track.py`` (``--acquire``: the rows of (d) only)."""
 import json
 import os
 import statistics
@@ -160,9 +163,47 @@ def forward_syncs(model, p):
     return sorted({str(w.message).split("(")[0].strip() for w in seen if "ynchron" in str(w.message) and "prototype" not in str(w.message)})
 
 
+def readout_alone_us(B, dtype=torch.bfloat16):
+    """hrp_kp_readout_fwd (both launches) on a [B, 30, 40, 2048] feature, device events over eager calls."""
+    from hrpe_amd import _native as nv
+    cin, k, hin, win = 2048, 7, 30, 40
+    x = torch.randn(B, hin, win, cin, device=DEV).to(dtype)
+    w = torch.randn(cin, k, 4, 4, device=DEV) * 2.0 ** -5
+    bias = torch.zeros(k, device=DEV)
+    dt = nv.HRP_BF16 if dtype == torch.bfloat16 else nv.HRP_F32
+    packed = torch.zeros(16 * cin * 32, dtype=dtype, device=DEV)
+    nv.call("hrp_kp_readout_pack", w.data_ptr(), cin, k, packed.data_ptr(), dt, None)
+    wsb = int(nv.lib().hrp_kp_readout_ws(B, hin))
+    ws, kp, ms = torch.zeros(wsb // 4, device=DEV), torch.zeros(B, k, 2, device=DEV), torch.zeros(B, k, 2, device=DEV)
+    return median_us(lambda: nv.call("hrp_kp_readout_fwd", x.data_ptr(), dt, B, hin, win, cin, cin, packed.data_ptr(), bias.data_ptr(), k,
+                                     -1.0, -1.0, 160.0, 120.0, kp.data_ptr(), ms.data_ptr(), ws.data_ptr(), wsb, None), warmup=10, reps=50)
+
+
+def bench_acquire(model, robot, B, seq):
+    """(d): detector + seed, and step with a detection every 30 frames."""
+    from hrpe_amd.lib.models.ctrnet.mask_inference import seg_mask_inference
+    torch.manual_seed(1)
+    det = seg_mask_inference((615.0, 615.0, 320.0, 240.0), "azure", image_hw=(H, W), allow_random_init=True).to(DEV)
+    det.set_compute_dtype(torch.bfloat16)
+    trk = PoseTracker(model, robot, K, (H, W), streams=B, device=DEV, detector=det.detect, detector_scale=det.args.scale,
+                      acquire_every=30)
+    trk.reset(seeds(B))
+    alat, athr = wall(lambda f: trk.acquire(f, force=True), seq, warmup=6, n=30)
+    lat, thr = wall(trk.step, seq, warmup=10, n=60)
+    return dict(B=B, row="acquire", acquire_latency_ms=round(alat, 3), acquire_pipelined_ms=round(athr, 3),
+                kp_readout_bf16_us=round(readout_alone_us(B), 1), kp_readout_fp32_us=round(readout_alone_us(B, torch.float32), 1),
+                step_acquire_every_30_latency_ms=round(lat, 3), step_acquire_every_30_pipelined_ms=round(thr, 3),
+                seed_status=trk.seed_status.cpu().tolist())
+
+
 def main():
     model = model_bf16()
     robot = URDFRobot("panda")
+    for B in (1, 4):
+        seq = [torch.from_numpy(np.stack([dream_scene.texture(H, W, 10 * t + b) for b in range(B)])).to(DEV) for t in range(4)]
+        print(json.dumps(bench_acquire(model, robot, B, seq)), flush=True)
+    if "--acquire" in sys.argv[1:]:
+        return
     for B in (1, 4, 16):
         seq = [torch.from_numpy(np.stack([dream_scene.texture(H, W, 10 * t + b) for b in range(B)])).to(DEV) for t in range(4)]
         eager, replay = bench_launches(B, seq[0])
