@@ -1178,7 +1178,7 @@ __device__ __forceinline__ void wgrad_fold_body(const hrp_wgrad_fold_desc& f, co
   }
 }
 
-static inline hrp_wgrad_fold_desc make_fold_desc(const hrp_wgrad_desc& d, int G, int pairs, int n_cib, int NTE, int NB) {
+__host__ __device__ static inline hrp_wgrad_fold_desc make_fold_desc(const hrp_wgrad_desc& d, int G, int pairs, int n_cib, int NTE, int NB) {
   hrp_wgrad_fold_desc f{};
   f.workspace = (const float*)d.workspace; f.dw = d.dw;
   f.G = G; f.pairs = pairs; f.n_cib = n_cib; f.nte = NTE; f.nb = NB;
@@ -1189,6 +1189,56 @@ static inline hrp_wgrad_fold_desc make_fold_desc(const hrp_wgrad_desc& d, int G,
 
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const hrp_wgrad_fold_desc f) {
   wgrad_fold_body(f, blockIdx.x, blockIdx.y);
+}
+
+// The end of both tilings, from the tile shape (TH, TW, TI, IHt, IWt, mindy, mindx) on: tile counts, the (cout, cin)
+// blocks of `cb` channels, the G pixel shares that `wg` workgroups give a block, and the divisors.
+// false: a tile that is not a border tile would reach outside the image.
+static bool wgrad_tile_grid(const hrp_wgrad_desc& d, WgradTiling& t, int cb, int wg, bool xcd) {
+  t.tiles_x = cdiv(d.Wo, t.TW); t.tiles_y = cdiv(d.Ho, t.TH); t.tiles_n = cdiv(d.N, t.TI);
+  t.ntiles = t.tiles_x * t.tiles_y * t.tiles_n;
+  // the DMA plan classifies a lane's validity per tile row / column class: only the first and the last tile
+  // row (column) may reach outside the image
+  if ((t.tiles_y >= 2 && (t.TH * d.in_stride + t.mindy < 0 ||
+                          (t.tiles_y - 2) * t.TH * d.in_stride + t.mindy + t.IHt - 1 >= d.H)) ||
+      (t.tiles_x >= 2 && (t.TW * d.in_stride + t.mindx < 0 ||
+                          (t.tiles_x - 2) * t.TW * d.in_stride + t.mindx + t.IWt - 1 >= d.W)))
+    return false;
+  t.n_cob = cdiv(d.Cout, cb); t.n_cib = cdiv(d.Cin, cb);
+  const int pairs = t.n_cob * t.n_cib;
+  int G = wg / pairs;   // each of a block's G workgroups walks ntiles / G pixel tiles
+  if (G < 1) G = 1;
+  if (G > t.ntiles) G = t.ntiles;
+  t.xmode = 0; t.xa = t.xb = t.xnb = 1;
+  // tuning knob: bit 0 mode 1, bit 1 mode 2.  Measured (PMC FETCH_SIZE of the weight-gradient launches of one step, B = 64):
+  // pair-major 27.1 GB, mode 2 only 22.1 GB, mode 1 only 28.5 GB, both 23.5 GB; kernel time one by one 8.31 / 8.75 / 8.38 /
+  // 8.78 ms; step time the same within 0.1 ms -> mode 2 (the 2 x 2 blocks of the 64-channel layers share an L2).
+  // The eight-wave tiling comes through here too: its launches follow the knob as well (they knew mode 2 only before)
+  static const int xmask = 2;
+  if (xcd) {          // batched launches (1-D grid): XCD-aware numbering
+    if (pairs >= 8 && pairs % 8 == 0 && (xmask & 1)) {
+      // xa | n_cob, xb | n_cib, (n_cob / xa) * (n_cib / xb) == 8, xa + xb minimal (slices fetched per XCD)
+      int best = 1 << 30;
+      for (int a = 1; a <= t.n_cob; ++a) {
+        if (t.n_cob % a) continue;
+        const int na = t.n_cob / a;
+        if (8 % na) continue;
+        const int nb_ = 8 / na;
+        if (t.n_cib % nb_) continue;
+        const int b = t.n_cib / nb_;
+        if (a + b < best) { best = a + b; t.xa = a; t.xb = b; t.xnb = nb_; t.xmode = 1; }
+      }
+    } else if ((pairs == 1 || pairs == 2 || pairs == 4) && G >= 8 && (xmask & 2)) {
+      G -= G % 8;
+      t.xmode = 2;
+    }
+  }
+  t.G = G;
+  t.fd_g = make_fastdiv(G);
+  t.fd_ihw = make_fastdiv(t.IHt * t.IWt); t.fd_iwt = make_fastdiv(t.IWt);
+  t.fd_thw = make_fastdiv(t.TH * t.TW); t.fd_tw = make_fastdiv(t.TW);
+  t.fd_tx = make_fastdiv(t.tiles_x); t.fd_ty = make_fastdiv(t.tiles_y); t.fd_cib = make_fastdiv(t.n_cib);
+  return true;
 }
 
 // wg_total: workgroups this problem may use (0: the single-launch default, about one per CU)
@@ -1240,54 +1290,14 @@ static int wgrad_tiling(const hrp_wgrad_desc& d, WgradTiling& t, int wg_budget =
     return HRP_ERR_ARG;
   }
   t.lds_bytes = lds;
-  t.tiles_x = cdiv(d.Wo, t.TW); t.tiles_y = cdiv(d.Ho, t.TH); t.tiles_n = cdiv(d.N, t.TI);
-  t.ntiles = t.tiles_x * t.tiles_y * t.tiles_n;
-  // the DMA plan classifies a lane's validity per tile row / column class: only the first and the last tile
-  // row (column) may reach outside the image
-  if ((t.tiles_y >= 2 && (t.TH * d.in_stride + mindy < 0 ||
-                          (t.tiles_y - 2) * t.TH * d.in_stride + mindy + t.IHt - 1 >= d.H)) ||
-      (t.tiles_x >= 2 && (t.TW * d.in_stride + mindx < 0 ||
-                          (t.tiles_x - 2) * t.TW * d.in_stride + mindx + t.IWt - 1 >= d.W))) {
+  // workgroups per (cout, cin) block: ~2 per CU over the whole launch
+  static const int wg_total = 256;   // (swept: DESIGN 5)
+  static const bool no_xcd = false;
+  if (!wgrad_tile_grid(d, t, 32 * NB, wg_budget > 0 ? wg_budget : wg_total, wg_budget > 0 && !no_xcd)) {
     set_error("wgrad: tap offsets reach beyond the border tiles (H=%d W=%d Ho=%d Wo=%d stride=%d)", d.H, d.W, d.Ho, d.Wo,
               d.in_stride);
     return HRP_ERR_ARG;
   }
-  t.n_cob = cdiv(d.Cout, 32 * NB); t.n_cib = cdiv(d.Cin, 32 * NB);
-  int pairs = t.n_cob * t.n_cib;
-  // workgroups per (cout, cin) block: ~2 per CU over the whole launch; each walks ntiles / G pixel tiles
-  static const int wg_total = 256;   // (swept: DESIGN 5)
-  int G = (wg_budget > 0 ? wg_budget : wg_total) / pairs;
-  if (G < 1) G = 1;
-  if (G > t.ntiles) G = t.ntiles;
-  t.xmode = 0; t.xa = t.xb = t.xnb = 1;
-  static const bool no_xcd = false;
-  // tuning knob: bit 0 mode 1, bit 1 mode 2.  Measured (PMC FETCH_SIZE of the weight-gradient launches of one step, B = 64):
-  // pair-major 27.1 GB, mode 2 only 22.1 GB, mode 1 only 28.5 GB, both 23.5 GB; kernel time one by one 8.31 / 8.75 / 8.38 /
-  // 8.78 ms; step time the same within 0.1 ms -> mode 2 (the 2 x 2 blocks of the 64-channel layers share an L2)
-  static const int xmask = 2;
-  if (wg_budget > 0 && !no_xcd) {          // batched launches (1-D grid): XCD-aware numbering
-    if (pairs >= 8 && pairs % 8 == 0 && (xmask & 1)) {
-      // xa | n_cob, xb | n_cib, (n_cob / xa) * (n_cib / xb) == 8, xa + xb minimal (slices fetched per XCD)
-      int best = 1 << 30;
-      for (int a = 1; a <= t.n_cob; ++a) {
-        if (t.n_cob % a) continue;
-        const int na = t.n_cob / a;
-        if (8 % na) continue;
-        const int nb_ = 8 / na;
-        if (t.n_cib % nb_) continue;
-        const int b = t.n_cib / nb_;
-        if (a + b < best) { best = a + b; t.xa = a; t.xb = b; t.xnb = nb_; t.xmode = 1; }
-      }
-    } else if ((pairs == 1 || pairs == 2 || pairs == 4) && G >= 8 && (xmask & 2)) {
-      G -= G % 8;
-      t.xmode = 2;
-    }
-  }
-  t.G = G;
-  t.fd_g = make_fastdiv(G);
-  t.fd_ihw = make_fastdiv(t.IHt * t.IWt); t.fd_iwt = make_fastdiv(t.IWt);
-  t.fd_thw = make_fastdiv(t.TH * t.TW); t.fd_tw = make_fastdiv(t.TW);
-  t.fd_tx = make_fastdiv(t.tiles_x); t.fd_ty = make_fastdiv(t.tiles_y); t.fd_cib = make_fastdiv(t.n_cib);
   return HRP_OK;
 }
 
@@ -1302,6 +1312,7 @@ static int octo_pairs(const hrp_wgrad_desc& d) {
   return (d.Cout % 64 == 0 && d.Cin % 64 == 0) ? 4 : 0;
 }
 
+// (no message with HRP_ERR_ARG: the callers fall back to smaller tiles or to the four-wave program)
 static int wgrad_tiling_octo(const hrp_wgrad_desc& d, WgradTiling& t, int pairs_w, int wg_budget, int nks = 4) {
   const bool x3 = d.dtype == HRP_F32X3;
   const int npl = pairs_w == 4 ? 2 : 1, BM = nks * 16 * (8 / pairs_w);
@@ -1331,44 +1342,63 @@ static int wgrad_tiling_octo(const hrp_wgrad_desc& d, WgradTiling& t, int pairs_
   t.ring = (!x3 && pairs_w == 4 && 3 * t.buf_bytes <= 160 * 1024) ? 3 : 2;
   t.lds_bytes = t.ring * t.buf_bytes > red_bytes ? t.ring * t.buf_bytes : red_bytes;
   if (t.lds_bytes > 160 * 1024) return HRP_ERR_ARG;
-  t.tiles_x = cdiv(d.Wo, TW); t.tiles_y = cdiv(d.Ho, TH); t.tiles_n = cdiv(d.N, TI);
-  t.ntiles = t.tiles_x * t.tiles_y * t.tiles_n;
-  if ((t.tiles_y >= 2 && (TH * IS - halo < 0 || (t.tiles_y - 2) * TH * IS - halo + t.IHt - 1 >= d.H)) ||
-      (t.tiles_x >= 2 && (TW * IS - halo < 0 || (t.tiles_x - 2) * TW * IS - halo + t.IWt - 1 >= d.W)))
-    return HRP_ERR_ARG;
-  t.n_cob = d.Cout / (32 * npl); t.n_cib = d.Cin / (32 * npl);
-  const int pairs = t.n_cob * t.n_cib;
-  int G = wg_budget / pairs;
-  if (G < 1) G = 1;
-  if (G > t.ntiles) G = t.ntiles;
-  t.xmode = 0; t.xa = t.xb = t.xnb = 1;
-  if ((pairs == 1 || pairs == 2 || pairs == 4) && G >= 8) { G -= G % 8; t.xmode = 2; }
-  t.G = G;
+  if (!wgrad_tile_grid(d, t, 32 * npl, wg_budget, true)) return HRP_ERR_ARG;
   t.use_ws = 1;
-  t.fd_g = make_fastdiv(G);
-  t.fd_ihw = make_fastdiv(t.IHt * t.IWt); t.fd_iwt = make_fastdiv(t.IWt);
-  t.fd_thw = make_fastdiv(TH * TW); t.fd_tw = make_fastdiv(TW);
-  t.fd_tx = make_fastdiv(t.tiles_x); t.fd_ty = make_fastdiv(t.tiles_y); t.fd_cib = make_fastdiv(t.n_cib);
   return HRP_OK;
 }
 
-// 64 x 64 blocks for the 1x1 bf16 layers with at least 64 channels on both sides
-template <typename T, int NT>
-static constexpr bool can_nb2() { return NT == 1 && Elem<T>::SZ == 2; }
-static inline bool want_nb2(const hrp_wgrad_desc& d) { return d.Cout >= 64 && d.Cin >= 64 && d.dw_cin >= 64; }
+// ---- one dispatch: (element type, tap count, NB) of a problem as a tag type --------------------------------------------------
+template <typename T_, int NT_, int NB_ = 1>
+struct WgradTag { using T = T_; static constexpr int NT = NT_, NB = NB_; };
+
+// f(WgradTag<T, NT>{}) for the element type and tap count (1, 4, else 9: wgrad_check admits no other)
+template <typename F>
+static auto wgrad_dispatch_nt(int dtype, int ntaps, F&& f) {
+  if (dtype == HRP_F32) {
+    if (ntaps == 1) return f(WgradTag<float, 1>{});
+    if (ntaps == 4) return f(WgradTag<float, 4>{});
+    return f(WgradTag<float, 9>{});
+  }
+  if (dtype == HRP_F32X3) {
+    if (ntaps == 1) return f(WgradTag<f32x3_t, 1>{});
+    if (ntaps == 4) return f(WgradTag<f32x3_t, 4>{});
+    return f(WgradTag<f32x3_t, 9>{});
+  }
+  if (ntaps == 1) return f(WgradTag<bf16_t, 1>{});
+  if (ntaps == 4) return f(WgradTag<bf16_t, 4>{});
+  return f(WgradTag<bf16_t, 9>{});
+}
+
+// f(WgradTag<T, NT, NB>{}) with the four-wave program's NB: 64 x 64 blocks for the 1x1 bf16 layers with at least 64 channels
+// on both sides
+template <typename T, int NT, typename F>
+static auto wgrad_with_nb(WgradTag<T, NT>, const hrp_wgrad_desc& d, F&& f) {
+  if constexpr (NT == 1 && Elem<T>::SZ == 2) {
+    if (d.Cout >= 64 && d.Cin >= 64 && d.dw_cin >= 64) return f(WgradTag<T, NT, 2>{});
+  }
+  return f(WgradTag<T, NT, 1>{});
+}
+template <typename F>
+static auto wgrad_dispatch(const hrp_wgrad_desc& d, F&& f) {
+  return wgrad_dispatch_nt(d.dtype, d.ntaps, [&](auto g) { return wgrad_with_nb(g, d, f); });
+}
+
+// Bytes of the partial slabs of a launch (G slabs of nte * 1024 floats for each of `pairs` blocks) and whether the
+// descriptor's workspace holds them: the one place that decides between slabs and atomics.
+struct WgradSlabs { int64_t bytes; bool fit; };
+static inline WgradSlabs wgrad_slabs(const hrp_wgrad_desc& d, int G, int pairs, int nte) {
+  const int64_t bytes = (int64_t)G * pairs * nte * 1024 * 4;
+  return {bytes, d.workspace && d.workspace_bytes >= bytes};
+}
+static inline WgradSlabs wgrad_slabs(const hrp_wgrad_desc& d, const WgradTiling& t, int nte) {
+  return wgrad_slabs(d, t.G, t.n_cob * t.n_cib, nte);
+}
 
 template <typename T, int NT, int NB>
-static int64_t wgrad_ws_bytes_nb(const hrp_wgrad_desc& d) {
+static int64_t wgrad_ws_bytes_nb(WgradTag<T, NT, NB>, const hrp_wgrad_desc& d) {
   WgradTiling t{};
   if (wgrad_tiling<T, NT, NB>(d, t) != HRP_OK) return 0;
-  return (int64_t)t.G * t.n_cob * t.n_cib * (NT * NB * NB) * 1024 * 4;
-}
-template <typename T, int NT>
-static int64_t wgrad_ws_bytes(const hrp_wgrad_desc& d) {
-  if constexpr (can_nb2<T, NT>()) {
-    if (want_nb2(d)) return wgrad_ws_bytes_nb<T, NT, 2>(d);
-  }
-  return wgrad_ws_bytes_nb<T, NT, 1>(d);
+  return wgrad_slabs(d, t, NT * NB * NB).bytes;
 }
 
 // bf16 / fp32x3: k-steps of 16 pixels per wave and tile, unrolled at compile time (fp32x3 tiles stop at 128 pixels); fp32: 0
@@ -1380,8 +1410,7 @@ template <typename T, int NT, int NB>
 static int wgrad_plan_single(const hrp_wgrad_desc& d, WgradTiling& t) {
   const int rc = wgrad_tiling<T, NT, NB>(d, t);
   if (rc != HRP_OK) return rc;
-  const int64_t need = (int64_t)t.G * t.n_cob * t.n_cib * (NT * NB * NB) * 1024 * 4;
-  t.use_ws = (d.workspace && d.workspace_bytes >= need) ? 1 : 0;
+  t.use_ws = wgrad_slabs(d, t, NT * NB * NB).fit ? 1 : 0;
   if (!t.use_ws && !d.accumulate && d.dw_tap_stride > 0 && d.dw_tap_stride != d.ntaps) {
     set_error("wgrad: a tap group without a workspace must accumulate (the caller zeroes dw)");
     return HRP_ERR_ARG;
@@ -1390,7 +1419,7 @@ static int wgrad_plan_single(const hrp_wgrad_desc& d, WgradTiling& t) {
 }
 
 template <typename T, int NT, int NB>
-static int launch_wgrad_nb(const hrp_wgrad_desc& d, hipStream_t s) {
+static int launch_wgrad_nb(WgradTag<T, NT, NB>, const hrp_wgrad_desc& d, hipStream_t s) {
   constexpr int NTE = NT * NB * NB;
   WgradTiling t{};
   int rc = wgrad_plan_single<T, NT, NB>(d, t);
@@ -1418,13 +1447,6 @@ static int launch_wgrad_nb(const hrp_wgrad_desc& d, hipStream_t s) {
   if (rc != HRP_OK || !t.use_ws || d.phase == 1) return rc;   // phase 1: the caller folds the slabs later
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(NTE * 1024 / FOLD_ELEMS, pairs), dim3(256), 0, s, make_fold_desc(d, t.G, pairs, t.n_cib, NTE, NB));
   return check_launch("wgrad_reduce_kernel");
-}
-template <typename T, int NT>
-static int launch_wgrad(const hrp_wgrad_desc& d, hipStream_t s) {
-  if constexpr (can_nb2<T, NT>()) {
-    if (want_nb2(d)) return launch_wgrad_nb<T, NT, 2>(d, s);
-  }
-  return launch_wgrad_nb<T, NT, 1>(d, s);
 }
 
 
@@ -1470,16 +1492,21 @@ __global__ __launch_bounds__(256) WGRAD_OCC void wgrad_batch_kernel(const WgradP
   }
 }
 
-// the eight-wave problems of a batch (nb >= 3): 512 threads per workgroup, so a launch of their own next to the others' launch
-__global__ __launch_bounds__(512) void wgrad_octo_batch_kernel(const WgradProblem* __restrict__ tab, const int n) {
+// The eight-wave problems of a batch (nb >= 3): 512 threads per workgroup, so a launch of their own next to the others'
+// launch.  The problem that owns this workgroup, and the workgroup's pixel share and block in it.
+__device__ __forceinline__ const WgradProblem& octo_problem_of(const WgradProblem* __restrict__ tab, const int n, int& gxi, int& blk) {
   int g = 0, base = 0;
   for (int i = 0; i < n; ++i) {
     const int b0 = tab[i].wblk0;
     if (tab[i].nb >= 3 && (int)blockIdx.x >= b0) { g = i; base = b0; }
   }
-  const WgradProblem& P = tab[g];
+  wgrad_block_of(tab[g].t, (int)blockIdx.x - base, gxi, blk);
+  return tab[g];
+}
+
+__global__ __launch_bounds__(512) void wgrad_octo_batch_kernel(const WgradProblem* __restrict__ tab, const int n) {
   int gxi, blk;
-  wgrad_block_of(P.t, (int)blockIdx.x - base, gxi, blk);
+  const WgradProblem& P = octo_problem_of(tab, n, gxi, blk);
   if (P.nb == 6 && P.nks == 2) conv_wgrad_octo_body<4, 2>(P.d, P.t, gxi, blk);
   else if (P.nb == 6) conv_wgrad_octo_body<4>(P.d, P.t, gxi, blk);
   else conv_wgrad_octo_body<1>(P.d, P.t, gxi, blk);
@@ -1487,14 +1514,8 @@ __global__ __launch_bounds__(512) void wgrad_octo_batch_kernel(const WgradProble
 
 template <int NT>
 __global__ __launch_bounds__(512) void wgrad_octo_x3_batch_kernel(const WgradProblem* __restrict__ tab, const int n) {
-  int g = 0, base = 0;
-  for (int i = 0; i < n; ++i) {
-    const int b0 = tab[i].wblk0;
-    if (tab[i].nb >= 3 && (int)blockIdx.x >= b0) { g = i; base = b0; }
-  }
-  const WgradProblem& P = tab[g];
   int gxi, blk;
-  wgrad_block_of(P.t, (int)blockIdx.x - base, gxi, blk);
+  const WgradProblem& P = octo_problem_of(tab, n, gxi, blk);
   if (P.nks == 4) conv_wgrad_octo_x3_body<NT, 4>(P.d, P.t, gxi, blk);
   else if (P.nks == 2) conv_wgrad_octo_x3_body<NT, 2>(P.d, P.t, gxi, blk);
   else if constexpr (NT == 9) conv_wgrad_octo_x3_body<NT, 1>(P.d, P.t, gxi, blk);     // (stride-2 layers: 32-pixel tiles)
@@ -1507,12 +1528,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const WgradProb
   const int local = (int)blockIdx.x - base;
   const int blk = fdiv(local, P.fd_r);
   const int bx = local - blk * (P.nte * 4);
-  hrp_wgrad_fold_desc f;
-  f.workspace = (const float*)P.d.workspace; f.dw = P.d.dw;
-  f.G = P.t.G; f.pairs = P.fold_pairs; f.n_cib = P.fold_n_cib; f.nte = P.nte; f.nb = P.fold_nb;
-  f.Cout = P.d.Cout; f.dw_cin = P.d.dw_cin; f.ntaps = P.d.ntaps; f.dw_tap_stride = P.d.dw_tap_stride; f.dw_tap_off = P.d.dw_tap_off;
-  f.accumulate = P.d.accumulate;
-  wgrad_fold_body(f, bx, blk);
+  wgrad_fold_body(make_fold_desc(P.d, P.t.G, P.fold_pairs, P.fold_n_cib, P.nte, P.fold_nb), bx, blk);
 }
 
 // ---- the deferred fold of up to HRP_BATCH_MAX phase-1 problems in one launch (any tap counts / element types) ----
@@ -1560,17 +1576,10 @@ static int wgrad_plan_one(const hrp_wgrad_desc& d, WgradProblem& P, int budget, 
     P.fd_r = make_fastdiv(P.nte * 4);
     return HRP_OK;
   }
-  P.nb = 1;
-  int rc;
-  if constexpr (can_nb2<T, NT>()) {
-    if (want_nb2(d)) P.nb = 2;
-  }
-  if (P.nb == 2) {
-    if constexpr (can_nb2<T, NT>()) rc = wgrad_tiling<T, NT, 2>(d, P.t, budget);
-    else rc = HRP_ERR_ARG;
-  } else {
-    rc = wgrad_tiling<T, NT, 1>(d, P.t, budget);
-  }
+  const int rc = wgrad_with_nb(WgradTag<T, NT>{}, d, [&](auto g) {
+    P.nb = decltype(g)::NB;
+    return wgrad_tiling<T, NT, decltype(g)::NB>(d, P.t, budget);
+  });
   if (rc != HRP_OK) return rc;
   P.nks = wgrad_nks<T>(P.t.BM);
   P.nte = NT * P.nb * P.nb;
@@ -1581,7 +1590,7 @@ static int wgrad_plan_one(const hrp_wgrad_desc& d, WgradProblem& P, int budget, 
 }
 
 template <typename T, int NT>
-static int wgrad_batch_prepare_nt(const hrp_wgrad_desc* descs, int n, WgradProblem* tab, hrp_batch_info* info) {
+static int wgrad_batch_prepare_nt(WgradTag<T, NT>, const hrp_wgrad_desc* descs, int n, WgradProblem* tab, hrp_batch_info* info) {
   WgradProblem probs[HRP_BATCH_MAX];
   double work[HRP_BATCH_MAX], total[2] = {0.0, 0.0};
   int octo[HRP_BATCH_MAX];
@@ -1611,11 +1620,11 @@ static int wgrad_batch_prepare_nt(const hrp_wgrad_desc* descs, int n, WgradProbl
     if (budget < P.pairs) budget = P.pairs;
     const int rc = wgrad_plan_one<T, NT>(descs[i], P, budget, octo[i]);
     if (rc != HRP_OK) return rc;
-    const int64_t need = (int64_t)P.t.G * P.fold_pairs * P.nte * 1024 * 4;
-    info->ws_bytes[i] = need;
+    const WgradSlabs slabs = wgrad_slabs(descs[i], P.t.G, P.fold_pairs, P.nte);
+    info->ws_bytes[i] = slabs.bytes;
     if (tab) {
-      HRP_REQUIRE(descs[i].workspace && descs[i].workspace_bytes >= need,
-                  "wgrad batch: problem %d needs %lld workspace bytes (has %lld)", i, (long long)need, (long long)descs[i].workspace_bytes);
+      HRP_REQUIRE(slabs.fit, "wgrad batch: problem %d needs %lld workspace bytes (has %lld)", i, (long long)slabs.bytes,
+                  (long long)descs[i].workspace_bytes);
       HRP_REQUIRE((uintptr_t)descs[i].workspace % 16 == 0, "wgrad batch: workspace alignment");
     }
     P.t.use_ws = 1;
@@ -1641,16 +1650,6 @@ static int wgrad_batch_prepare_nt(const hrp_wgrad_desc* descs, int n, WgradProbl
   return HRP_OK;
 }
 
-template <typename T>
-static int wgrad_batch_prepare_t(const hrp_wgrad_desc* descs, int n, void* table, hrp_batch_info* info) {
-  WgradProblem* tab = (WgradProblem*)table;
-  switch (descs[0].ntaps) {
-    case 1: return wgrad_batch_prepare_nt<T, 1>(descs, n, tab, info);
-    case 4: return wgrad_batch_prepare_nt<T, 4>(descs, n, tab, info);
-    default: return wgrad_batch_prepare_nt<T, 9>(descs, n, tab, info);
-  }
-}
-
 int wgrad_batch_prepare(const hrp_wgrad_desc* descs, int n, void* table, hrp_batch_info* info) {
   for (int i = 0; i < n; ++i) {
     const int rc = wgrad_check(&descs[i]);
@@ -1658,13 +1657,13 @@ int wgrad_batch_prepare(const hrp_wgrad_desc* descs, int n, void* table, hrp_bat
     HRP_REQUIRE(descs[i].ntaps == descs[0].ntaps && descs[i].dtype == descs[0].dtype, "wgrad batch: mixed tap counts / element types");
     HRP_REQUIRE(descs[i].phase == descs[0].phase, "wgrad batch: mixed phases");
   }
-  if (descs[0].dtype == HRP_F32) return wgrad_batch_prepare_t<float>(descs, n, table, info);
-  if (descs[0].dtype == HRP_F32X3) return wgrad_batch_prepare_t<f32x3_t>(descs, n, table, info);
-  return wgrad_batch_prepare_t<bf16_t>(descs, n, table, info);
+  return wgrad_dispatch_nt(descs[0].dtype, descs[0].ntaps, [&](auto g) {
+    return wgrad_batch_prepare_nt(g, descs, n, (WgradProblem*)table, info);
+  });
 }
 
 template <typename T, int NT>
-static int wgrad_batch_launch_nt(const WgradProblem* tab, const hrp_batch_info* info, hipStream_t s) {
+static int wgrad_batch_launch_nt(WgradTag<T, NT>, const WgradProblem* tab, const hrp_batch_info* info, hipStream_t s) {
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)wgrad_batch_kernel<T, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1691,28 +1690,10 @@ static int wgrad_batch_launch_nt(const WgradProblem* tab, const hrp_batch_info* 
 }
 
 int wgrad_batch_launch(const void* table_dev, const hrp_batch_info* info, hipStream_t s) {
-  const WgradProblem* tab = (const WgradProblem*)table_dev;
-  if (info->dtype == HRP_F32) {
-    switch (info->variant) {
-      case 1: return wgrad_batch_launch_nt<float, 1>(tab, info, s);
-      case 4: return wgrad_batch_launch_nt<float, 4>(tab, info, s);
-      case 9: return wgrad_batch_launch_nt<float, 9>(tab, info, s);
-    }
-  } else if (info->dtype == HRP_F32X3) {
-    switch (info->variant) {
-      case 1: return wgrad_batch_launch_nt<f32x3_t, 1>(tab, info, s);
-      case 4: return wgrad_batch_launch_nt<f32x3_t, 4>(tab, info, s);
-      case 9: return wgrad_batch_launch_nt<f32x3_t, 9>(tab, info, s);
-    }
-  } else {
-    switch (info->variant) {
-      case 1: return wgrad_batch_launch_nt<bf16_t, 1>(tab, info, s);
-      case 4: return wgrad_batch_launch_nt<bf16_t, 4>(tab, info, s);
-      case 9: return wgrad_batch_launch_nt<bf16_t, 9>(tab, info, s);
-    }
-  }
-  set_error("wgrad batch: bad variant %d", info->variant);
-  return HRP_ERR_ARG;
+  HRP_REQUIRE(info->variant == 1 || info->variant == 4 || info->variant == 9, "wgrad batch: bad variant %d", info->variant);
+  return wgrad_dispatch_nt(info->dtype, info->variant, [&](auto g) {
+    return wgrad_batch_launch_nt(g, (const WgradProblem*)table_dev, info, s);
+  });
 }
 
 int64_t wgrad_batch_table_bytes(int n) { return (int64_t)n * sizeof(WgradProblem); }
@@ -1746,23 +1727,14 @@ int wgrad_fold_launch(const void* table_dev, const hrp_batch_info* info, hipStre
   return check_launch("wgrad_fold_batch_kernel");
 }
 
+// (a tap group without a workspace is no error here: the descriptor then says G = 0, nothing to fold)
 template <typename T, int NT, int NB>
-static int fold_desc_nb(const hrp_wgrad_desc& d, hrp_wgrad_fold_desc* out) {
+static int fold_desc_nb(WgradTag<T, NT, NB>, const hrp_wgrad_desc& d, hrp_wgrad_fold_desc* out) {
   WgradTiling t{};
   const int rc = wgrad_tiling<T, NT, NB>(d, t);
   if (rc != HRP_OK) return rc;
-  const int pairs = t.n_cob * t.n_cib;
-  const int64_t need = (int64_t)t.G * pairs * (NT * NB * NB) * 1024 * 4;
-  const bool use_ws = d.workspace && d.workspace_bytes >= need;   // (as launch_wgrad_nb decides)
-  *out = make_fold_desc(d, use_ws ? t.G : 0, pairs, t.n_cib, NT * NB * NB, NB);
+  *out = make_fold_desc(d, wgrad_slabs(d, t, NT * NB * NB).fit ? t.G : 0, t.n_cob * t.n_cib, t.n_cib, NT * NB * NB, NB);
   return HRP_OK;
-}
-template <typename T, int NT>
-static int fold_desc_t(const hrp_wgrad_desc& d, hrp_wgrad_fold_desc* out) {
-  if constexpr (can_nb2<T, NT>()) {
-    if (want_nb2(d)) return fold_desc_nb<T, NT, 2>(d, out);
-  }
-  return fold_desc_nb<T, NT, 1>(d, out);
 }
 
 // ---- what a launch will run (hrp_wgrad_config) ------------------------------------------------------------------
@@ -1779,19 +1751,12 @@ static hrp_wgrad_config make_config(const hrp_wgrad_desc& d, const WgradTiling& 
   return c;
 }
 template <typename T, int NT, int NB>
-static int config_nb(const hrp_wgrad_desc& d, hrp_wgrad_config* out) {
+static int config_nb(WgradTag<T, NT, NB>, const hrp_wgrad_desc& d, hrp_wgrad_config* out) {
   WgradTiling t{};
   const int rc = wgrad_plan_single<T, NT, NB>(d, t);
   if (rc != HRP_OK) return rc;
   *out = make_config(d, t, wgrad_nks<T>(t.BM), NB);
   return HRP_OK;
-}
-template <typename T, int NT>
-static int config_t(const hrp_wgrad_desc& d, hrp_wgrad_config* out) {
-  if constexpr (can_nb2<T, NT>()) {
-    if (want_nb2(d)) return config_nb<T, NT, 2>(d, out);
-  }
-  return config_nb<T, NT, 1>(d, out);
 }
 
 }  // namespace hrp
@@ -1801,19 +1766,7 @@ extern "C" int hrp_wgrad_config_of(const hrp_wgrad_desc* d, hrp_wgrad_config* ou
   HRP_REQUIRE(out, "wgrad config: null pointer");
   const int crc = wgrad_check(d);
   if (crc != HRP_OK) return crc;
-  if (d->dtype == HRP_F32) {
-    if (d->ntaps == 1) return config_t<float, 1>(*d, out);
-    if (d->ntaps == 4) return config_t<float, 4>(*d, out);
-    return config_t<float, 9>(*d, out);
-  }
-  if (d->dtype == HRP_F32X3) {
-    if (d->ntaps == 1) return config_t<f32x3_t, 1>(*d, out);
-    if (d->ntaps == 4) return config_t<f32x3_t, 4>(*d, out);
-    return config_t<f32x3_t, 9>(*d, out);
-  }
-  if (d->ntaps == 1) return config_t<bf16_t, 1>(*d, out);
-  if (d->ntaps == 4) return config_t<bf16_t, 4>(*d, out);
-  return config_t<bf16_t, 9>(*d, out);
+  return wgrad_dispatch(*d, [&](auto g) { return config_nb(g, *d, out); });
 }
 
 extern "C" int hrp_batch_wgrad_configs(const void* table_host, const hrp_batch_info* info, hrp_wgrad_config* out) {
@@ -1829,19 +1782,7 @@ extern "C" int hrp_wgrad_fold_desc_of(const hrp_wgrad_desc* d, hrp_wgrad_fold_de
   HRP_REQUIRE(out, "wgrad fold: null pointer");
   const int crc = wgrad_check(d);
   if (crc != HRP_OK) return crc;
-  if (d->dtype == HRP_F32) {
-    if (d->ntaps == 1) return fold_desc_t<float, 1>(*d, out);
-    if (d->ntaps == 4) return fold_desc_t<float, 4>(*d, out);
-    return fold_desc_t<float, 9>(*d, out);
-  }
-  if (d->dtype == HRP_F32X3) {
-    if (d->ntaps == 1) return fold_desc_t<f32x3_t, 1>(*d, out);
-    if (d->ntaps == 4) return fold_desc_t<f32x3_t, 4>(*d, out);
-    return fold_desc_t<f32x3_t, 9>(*d, out);
-  }
-  if (d->ntaps == 1) return fold_desc_t<bf16_t, 1>(*d, out);
-  if (d->ntaps == 4) return fold_desc_t<bf16_t, 4>(*d, out);
-  return fold_desc_t<bf16_t, 9>(*d, out);
+  return wgrad_dispatch(*d, [&](auto g) { return fold_desc_nb(g, *d, out); });
 }
 
 extern "C" int hrp_batch_wgrad_fold_descs(const void* table_host, const hrp_batch_info* info, hrp_wgrad_fold_desc* out) {
@@ -1857,36 +1798,11 @@ extern "C" int hrp_conv2d_bwd_weight(const hrp_wgrad_desc* d, void* stream) {
   using namespace hrp;
   const int crc = wgrad_check(d);
   if (crc != HRP_OK) return crc;
-  hipStream_t s = (hipStream_t)stream;
-  if (d->dtype == HRP_F32) {
-    if (d->ntaps == 1) return launch_wgrad<float, 1>(*d, s);
-    if (d->ntaps == 4) return launch_wgrad<float, 4>(*d, s);
-    return launch_wgrad<float, 9>(*d, s);
-  }
-  if (d->dtype == HRP_F32X3) {
-    if (d->ntaps == 1) return launch_wgrad<f32x3_t, 1>(*d, s);
-    if (d->ntaps == 4) return launch_wgrad<f32x3_t, 4>(*d, s);
-    return launch_wgrad<f32x3_t, 9>(*d, s);
-  }
-  if (d->ntaps == 1) return launch_wgrad<bf16_t, 1>(*d, s);
-  if (d->ntaps == 4) return launch_wgrad<bf16_t, 4>(*d, s);
-  return launch_wgrad<bf16_t, 9>(*d, s);
+  return wgrad_dispatch(*d, [&](auto g) { return launch_wgrad_nb(g, *d, (hipStream_t)stream); });
 }
 
 extern "C" int64_t hrp_wgrad_workspace_bytes(const hrp_wgrad_desc* d) {
   using namespace hrp;
   if (!d) return 0;
-  if (d->dtype == HRP_F32) {
-    if (d->ntaps == 1) return wgrad_ws_bytes<float, 1>(*d);
-    if (d->ntaps == 4) return wgrad_ws_bytes<float, 4>(*d);
-    return wgrad_ws_bytes<float, 9>(*d);
-  }
-  if (d->dtype == HRP_F32X3) {
-    if (d->ntaps == 1) return wgrad_ws_bytes<f32x3_t, 1>(*d);
-    if (d->ntaps == 4) return wgrad_ws_bytes<f32x3_t, 4>(*d);
-    return wgrad_ws_bytes<f32x3_t, 9>(*d);
-  }
-  if (d->ntaps == 1) return wgrad_ws_bytes<bf16_t, 1>(*d);
-  if (d->ntaps == 4) return wgrad_ws_bytes<bf16_t, 4>(*d);
-  return wgrad_ws_bytes<bf16_t, 9>(*d);
+  return wgrad_dispatch(*d, [&](auto g) { return wgrad_ws_bytes_nb(g, *d); });
 }
