@@ -90,7 +90,7 @@ class TensorH:
         self.grad_buf()
         root = self.base if self.base is not None else self
         root.grad_written = True     # (a column slice's gradient lives in its root's buffer: the root's producer must run)
-        self.plan.grad_owner[self.gptr()] = root      # who writes this gradient, for Plan._fuse_bn_reduce
+        self.plan.grad_owner[self.gptr()] = root      # who writes this gradient, for plan_passes.fuse_bn_reduce
         here = self.plan.lane_path
         if any(lanes_concurrent(here, q) for q in root._grad_paths):
             raise RuntimeError("plan: a gradient is accumulated from two concurrent lanes")
@@ -146,31 +146,24 @@ class ParamW:
         self.src = None          # fp32 tensor packed instead of `param` (derived layouts, e.g. the 4x4 form of the stem)
 
 
-# ReLU sign bits written by the forward element-wise pass, read by its backward instead of the activation
-RELU_BITMASK = True
-
 # True: every lane runs on the caller's stream (per-kernel timing passes, A/B measurements)
 SERIAL_LANES = bool(os.environ.get("HRP_SERIAL_LANES"))
-
 
 # nesting depth of parallel blocks that really fork; deeper ones stay on their parent lane.  1 = flat: a lane
 # forked from a forked lane crashes hipStreamEndCapture on ROCm 7 (eager multi-stream execution is fine)
 MAX_LANE_DEPTH = 1
 
-
-# How a plan executes.  "merged" (default): ONE stream; the lanes of every parallel block are walked in lock step and
+# How a plan executes.  "merged": ONE stream; the lanes of every parallel block are walked in lock step and
 # the launches of one kernel family that sit at the same position of their lanes - the same layer of every branch of
 # both trunks - become ONE batched launch (hrp_batch_*, include/hrp.h).  "lanes": every lane is a HIP stream forked
 # from / joined into its parent (round 1; still what the measurements of the batched launches are compared with).
-# "hybrid": parallel blocks that asked for streams keep them (one per trunk), the virtual blocks inside each stream are
-# merged - two chains of batched launches whose ramp-up / tail phases overlap.
+# "hybrid" (default): parallel blocks that asked for streams keep them (one per trunk), the virtual blocks inside each stream
+# are merged - two chains of batched launches whose ramp-up / tail phases overlap.
 PLAN_MODE = os.environ.get("HRP_PLAN_MODE", "hybrid")
+BATCHING = True      # False (tests): merged mode without batching = the same launches one by one
 # merged / hybrid: weight-gradient launches write their partial slabs only (descriptor phase 1); the slabs of up to 32
 # layers are folded into the gradients by ONE launch at the end of their lane (or every WGRAD_FOLD_EVERY problems)
 # instead of a 6-10 us launch behind every weight-gradient launch (~660 per step of the benchmark network)
-# the BatchNorm-backward reduce pass of an activation whose gradient has ONE producer, a data-gradient convolution, runs in
-# that convolution's epilogue (hrp_conv_desc.bnb_*) instead of as a launch of its own over the same two tensors
-FUSE_BN_REDUCE = True
 WGRAD_DEFER = True
 WGRAD_FOLD_EVERY = 32
 # weight gradients feed nothing before the optimizer: the launches of a lane are held back until WGRAD_SINK problems of one
@@ -180,21 +173,18 @@ WGRAD_FOLD_EVERY = 32
 # twice the problems write (and the folds read) half the slab bytes - 35.17 -> 34.52 ms per step (8 / 12 / 16 / 20 / 24 / 32:
 # 35.9 / 35.9 / 35.4 / 35.3* / 35.5 / 35.6 on one box, * 35.3 against 34.5 for 16 on another)
 WGRAD_SINK = int(os.environ.get("HRP_WGRAD_SINK", "16"))
-# train-mode BasicBlock interiors conv -> BN -> ReLU -> conv on the row-strip kernel (csrc/conv_row.h): the BatchNorm + ReLU
-# runs in the second convolution's staging path, its backward in the staging path of the first convolution's data gradient
 # stride-2 data gradients: parity classes padded to 4 taps (PlanBuilder._conv_bwd)
 PARITY_PAD = True
+# train-mode BasicBlock interiors conv -> BN -> ReLU -> conv on the row-strip kernel (csrc/conv_row.h): the BatchNorm + ReLU
+# runs in the second convolution's staging path, its backward in the staging path of the first convolution's data gradient
 ROWCONV_FUSE = True
 # ... and the block-end activation's backward (apply pass into conv2's data gradient, reduce pass into the next block's)
 BLOCK_END_FUSE = True
-BLOCK_END_REDUCE_FUSE = True
-BLOCK_FUSE = os.environ.get("HRP_BLOCK_FUSE", "1") not in ("0", "")      # fused inference BasicBlock (csrc/conv_block.h)
-# ... with the shortcut's gradient added by conv1's data gradient as a masked residual (one write of the block input's gradient)
-MASKED_RES = True
 # ... and the block-end FORWARD pass, out = relu(bn2(y2) + x), inside the NEXT block's conv1 (row-strip pro_mode 3: the raw y2 rows are
 # staged, bn + shortcut + ReLU applied in place, `out` and its ReLU bits leave as side outputs): three of the four block ends of a
 # branch stack lose their hrp_ew_fwd launch and conv1 no longer reads `out` back
 BLOCK_END_FWD_FUSE = os.environ.get("HRP_BLOCK_END_FWD", "1") not in ("0", "")
+BLOCK_FUSE = os.environ.get("HRP_BLOCK_FUSE", "1") not in ("0", "")      # fused inference BasicBlock (csrc/conv_block.h)
 # train-mode Bottlenecks at >= 131 072 pixels (layer1, the first incre-module of the cls head): conv3 (+ the 1x1 projection of the
 # shortcut) + BatchNorm + shortcut + ReLU as pointwise launches that never store a raw 1x1 output, the BatchNorm backward likewise
 # (PlanBuilder.bottleneck_tail)
@@ -206,24 +196,19 @@ BNECK_TAIL_FUSE = os.environ.get("HRP_TAIL_FUSE", "1") not in ("0", "")
 POOL_FUSE_GRADS = os.environ.get("HRP_POOL_FUSE", "0") not in ("0", "")
 # external images are converted (NCHW fp32 / bytes -> NHWC) in the lane of their first reader (PlanBuilder.image_input)
 LAZY_INPUTS = os.environ.get("HRP_LAZY_INPUTS", "1") not in ("0", "")
-ARENA_ZERO_EARLY = True
-BATCHING = True      # False (tests): merged mode without batching = the same launches one by one
-# lanes of DIFFERENT launch sequences (the paths of a fuse layer) merge by their heads - the largest group of equal merge key first -
-# instead of by position: 646 -> 628 conv launches, 34.12 -> 33.87 ms per step (A/B/A/B on one box)
-GREEDY_MERGE = True
-# development aid (set by tests / tools): batch only these families ({"conv", "wgrad", "ew_fwd", "ew_red", "ew_app"})
-BATCH_FAMILIES = None
-# The switches above without an environment variable are module constants: tests and tools patch them (plan.X = ...) before a
-# plan is built.  The environment variables that remain are the ones a user of the library or of bench.py needs: HRP_PLAN_MODE,
-# HRP_SERIAL_LANES, HRP_WGRAD_SINK, HRP_BLOCK_FUSE, HRP_PLAN_STATS, HRP_DBG_SYNC.
 PLAN_STATS = bool(os.environ.get("HRP_PLAN_STATS"))      # print launch counts per family when a plan is finalised
 DBG_SYNC = os.environ.get("HRP_DBG_SYNC")                 # development aid: device-wide sync after every op / every fork and join
+# The switches above without an environment variable - MAX_LANE_DEPTH, BATCHING, WGRAD_DEFER, WGRAD_FOLD_EVERY, PARITY_PAD,
+# ROWCONV_FUSE, BLOCK_END_FUSE - are module constants: tests and tools patch them (plan.X = ...) before a plan is built and use the
+# other setting as their reference.  The environment variables are for a user of the library or of bench.py:
+# HRP_PLAN_MODE, HRP_SERIAL_LANES, HRP_WGRAD_SINK, HRP_BLOCK_FUSE, HRP_BLOCK_END_FWD, HRP_TAIL_FUSE, HRP_POOL_FUSE, HRP_LAZY_INPUTS,
+# HRP_PLAN_STATS, HRP_DBG_SYNC.
 
-# bumped whenever parameters / BatchNorm buffers are modified behind torch's back (see Plan.params_dirty)
 # largest dilation of a 3x3 convolution the tile program runs as ONE problem (its halo tile must fit LDS); beyond it
 # PlanBuilder._conv_shifted_taps splits the taps into one-tap problems
 MAX_TILE_DILATION = 4
 
+# bumped whenever parameters / BatchNorm buffers are modified behind torch's back (see Plan.params_dirty)
 PARAM_EPOCH = 0
 _PLAN_SERIAL = 0      # plans of this process that drew a dropout key (Plan.rng_state)
 
@@ -256,7 +241,36 @@ FAMILIES = {"conv": (nv.BATCH_CONV, "hrp_conv2d_fwd", nv.ConvDesc),
             "wgrad_fold": (nv.BATCH_WGRAD_FOLD, None, nv.WgradFoldDesc)}
 
 
-class Launch:
+class LaunchOp:
+    """An entry of a launch list that is a kernel launch with descriptors - not a plain closure, not a lane marker: its family,
+    the single launches it stands for and the key under which the lock-step merge may batch it."""
+    __slots__ = ()
+    fam = None
+
+    def launches(self):
+        return [self]
+
+    def merge_key(self):
+        """Launches with equal keys may share a batched launch; None: always alone."""
+        return None
+
+    def set_ws(self, regions):
+        """Weight gradients: the (workspace, workspace_bytes) of every problem into its descriptor."""
+        for it, (ws, nbytes) in zip(self.launches(), regions):
+            it.desc.workspace, it.desc.workspace_bytes = ws, nbytes
+
+
+def is_fam(op, *fams):
+    """Is this op a launch of one of these kernel families?  (False for plain closures and lane markers.)"""
+    return isinstance(op, LaunchOp) and op.fam in fams
+
+
+def marker_kind(e):
+    """Entry -> "fork" / "join" / "pack_join" for a marker between lanes, None for an op that runs on a lane."""
+    return e.op.kind if e.lane is None else None
+
+
+class Launch(LaunchOp):
     """One launch of a batchable family: (family, descriptor).  Callable like the plain closures of the launch lists."""
     __slots__ = ("fam", "desc")
 
@@ -266,8 +280,9 @@ class Launch:
     def __call__(self, s):
         nv.call(FAMILIES[self.fam][1], C.byref(self.desc), s)
 
-    def launches(self):
-        return [self]
+    def ws_need(self, alone=True):
+        """Weight gradient: -> [scratch bytes of the launch]."""
+        return [int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(self.desc)))]
 
     def fold_desc(self):
         """Phase-1 weight gradient launched on its own: the fold descriptor of the tiling the launcher will choose."""
@@ -279,10 +294,7 @@ class Launch:
         return [self.fold_desc()]
 
     def merge_key(self):
-        """Launches with equal keys may share a batched launch; None: always alone."""
         d = self.desc
-        if BATCH_FAMILIES is not None and self.fam not in BATCH_FAMILIES:
-            return None
         esz = 2 if d.dtype == nv.HRP_BF16 else 4
         if self.fam == "conv":
             if d.ntaps not in (1, 2, 4, 9) or (d.Cin * esz) % 32 or (d.dtype != nv.HRP_BF16 and d.H == 1 and d.W == 1 and d.Cin >= 512):
@@ -311,8 +323,8 @@ class Launch:
         return tuple(x for x in (d.din, d.din2) if x)
 
 
-class BatchLaunch:
-    """Launches of one family (one per concurrent lane) as ONE launch; built by Plan._flatten, prepared at finalize."""
+class BatchLaunch(LaunchOp):
+    """Launches of one family (one per concurrent lane) as ONE launch; built by plan_passes.flatten, prepared at finalize."""
 
     def __init__(self, plan, items):
         self.plan, self.items = plan, list(items)
@@ -325,13 +337,14 @@ class BatchLaunch:
     def merge_key(self):
         return self.items[0].merge_key()
 
-    def ws_query(self):
-        """-> workspace bytes per problem (weight gradients)."""
+    def ws_need(self, alone=True):
+        """Weight gradients: -> scratch bytes per problem of the batched launch.  alone: at least what the problem takes as a single
+        launch too, for a batch that prepare() refuses and that runs one by one (False: the caller gives such a batch other scratch)."""
         n = len(self.items)
         arr = (nv.WgradDesc * n)(*[it.desc for it in self.items])
         info = nv.BatchInfo()
         nv.check(nv.lib().hrp_batch_prepare(nv.BATCH_WGRAD, arr, n, None, C.byref(info)), "hrp_batch_prepare")
-        return [int(info.ws_bytes[i]) for i in range(n)]
+        return [max(int(info.ws_bytes[i]), it.ws_need()[0] if alone else 0) for i, it in enumerate(self.items)]
 
     def prepare(self):
         famid, _, dtype = FAMILIES[self.fam]
@@ -355,8 +368,7 @@ class BatchLaunch:
             folds = (nv.WgradFoldDesc * n)()
             nv.check(nv.lib().hrp_batch_wgrad_fold_descs(host, C.byref(info), folds), "hrp_batch_wgrad_fold_descs")
             self.folds = list(folds)
-        self.table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.plan.device)
-        self.plan.keep.append(self.table)
+        self.table = self.plan.upload(host)
 
     def fold_descs(self):
         """Phase-1 weight gradients: the fold descriptors of the problems (after prepare)."""
@@ -372,7 +384,7 @@ class BatchLaunch:
             nv.call_batch(self, s)
 
 
-class BlockLaunch:
+class BlockLaunch(LaunchOp):
     """One fused inference BasicBlock (csrc/conv_block.h, descriptor nv.BlockDesc).  The lock-step merge pairs the 32- and the
     64-channel block of one position into one hrp_block_launch; alone it is a launch of one problem."""
     fam = "block"
@@ -380,9 +392,6 @@ class BlockLaunch:
     def __init__(self, desc):
         self.desc = desc
         self._single = None
-
-    def launches(self):
-        return [self]
 
     def merge_key(self):
         return ("block",)
@@ -396,7 +405,7 @@ class BlockLaunch:
         self._single(s)
 
 
-class BlockBatch:
+class BlockBatch(LaunchOp):
     """hrp_block_launch of one problem, or of the 32-channel + the 64-channel block of one lock-step position."""
     fam = "block"
 
@@ -406,9 +415,6 @@ class BlockBatch:
 
     def launches(self):
         return self.items
-
-    def merge_key(self):
-        return None
 
     def prepare(self):
         n = len(self.items)
@@ -438,6 +444,7 @@ def _pair_block(plan, ops):
 
 def _merge_ops(plan, ops):
     """Ops of equal merge key -> batched launches of at most BATCH_MAX problems with pairwise distinct outputs."""
+    # (not plan_passes.take_distinct, a stable partition: here a conflict closes the running group and nothing is carried past it)
     items = [l for op in ops for l in op.launches()]
     out, cur, seen = [], [], set()
     for it in items:
@@ -477,6 +484,7 @@ class _LaneSync:
 
 class _PackJoin:
     """Forward-list entry: the main lane waits for the side stream that packs the late weights (Plan.run_prep)."""
+    kind = "pack_join"
 
     def __init__(self, plan):
         self.plan = plan
@@ -667,16 +675,51 @@ class Plan:
         dev = self.device
         self.stats = torch.zeros(max(self.stats_floats, 2), dtype=torch.float64, device=dev)       # fp64 slots (include/hrp.h)
         self.bsums = torch.zeros(max(self.bsums_floats, 2), dtype=torch.float64, device=dev)
-        # packed weights: separate arenas per element type.  Training plans with parallel blocks pack in two parts:
-        # the weights of the first block (stem, layer1) on the main stream, the rest (99 % of the bytes) on a side
-        # stream that the forward list joins right after that block - the 0.7 ms gather runs under the stem instead of
-        # in front of it.  `cut` = index in fwd of the join.
+        # Training plans with parallel blocks pack their weights in two parts: the weights of the first block (stem, layer1) on the
+        # main stream, the rest (99 % of the bytes) on a side stream that the forward list joins right after that block - the
+        # 0.7 ms gather runs under the stem instead of in front of it.  `cut` = index in fwd of the join.
+        cut = self._late_pack_cut()
+        self._layout_packed_weights(cut)
+        self._pack_stream = None
+        self._arena_clean = False      # the gradient arena was zeroed by this forward's run_prep (side stream)
+        if self._pack_tables_late:
+            self._pack_stream = torch.cuda.Stream(device=dev)
+            list.insert(self.fwd, cut, Entry(None, (), _PackJoin(self)))
+        self.merged = PLAN_MODE in ("merged", "hybrid")
+        if not self.merged:
+            self.wgrad_ws = {lane: torch.zeros(max(nb // 4, 4), dtype=torch.float32, device=dev)
+                             for lane, nb in self.wgrad_ws_bytes.items()}
+        # resolve deferred pointers (merged: the weight-gradient scratch is assigned below, once the batches are known)
+        for fn in self._late:
+            fn()
+        self._late = []
+        if self.need_grad:
+            passes.fuse_bn_reduce(self)
+        if self.merged:
+            # lock-step merge of the virtual lanes into batched launches; streams only where a block asked for them
+            self.fwd_run, self.bwd_run = passes.flatten(self, self.fwd), passes.flatten(self, self.bwd)
+            if WGRAD_SINK > 1 and WGRAD_DEFER and BATCHING:
+                self.bwd_run = passes.sink_wgrads(self, self.bwd_run)
+            if passes.assign_wgrad_scratch(self):      # (also prepares every batched launch: the pointers are final)
+                self.bwd_run = passes.insert_folds(self, self.bwd_run)
+            used = {e.lane for e in self.fwd_run + self.bwd_run if e.lane is not None}
+            self._side_streams = [torch.cuda.Stream(device=dev) if (i + 1) in used else None for i in range(self.n_lanes - 1)]
+        else:
+            self._side_streams = [torch.cuda.Stream(device=dev) for _ in range(self.n_lanes - 1)]
+        self._bn_tables()
+        self.built = True
+        if PLAN_STATS:
+            self._print_stats()
+
+    def _layout_packed_weights(self, cut):
+        """Packed weights: one arena per element type, every weight's forward (and, need_t, transposed) packing at a 64-element
+        boundary, and the tables of the pack launches - the weights first used before fwd[cut] (cut None: all) in _pack_tables, the
+        others in _pack_tables_late."""
         self._pack_tables, self._pack_tables_late = [], []
         for w in self.weight_list:
             # the tap stride of the transposed packing is ntaps + pad_t for EVERY data gradient of the weight: a use that was
             # emitted with another w_ntaps (a weight shared by a padded and an unpadded stride-2 layer) would read shifted taps
             assert all(t == w.ntaps + w.pad_t for t in w.t_ntaps), f"plan: data gradients of one weight disagree on its tap slots ({w.t_ntaps}, pad_t {w.pad_t})"
-        cut = self._late_pack_cut()
         for dtype in (torch.float32, torch.bfloat16):
             ws = [w for w in self.weight_list if w.dtype == dtype]
             if not ws:
@@ -694,7 +737,7 @@ class Plan:
                     w.bwd_off = total
                     total += _rup(nb, 64)
                     w.max_elems = max(nf, nb)
-            arena = torch.zeros(total, dtype=dtype, device=dev)
+            arena = torch.zeros(total, dtype=dtype, device=self.device)
             self.keep.append(arena)
             for w in ws:
                 w.arena = arena
@@ -709,140 +752,42 @@ class Plan:
                     tab[i].dst = arena.data_ptr() + w.fwd_off * esz
                     tab[i].dst_t = (arena.data_ptr() + w.bwd_off * esz) if w.need_t else None
                     tab[i].Cout, tab[i].Cin, tab[i].ntaps, tab[i].pad_t = w.cout, w.cin, w.ntaps, w.pad_t
-                tdev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+                tdev = self.upload(tab)
                 # compact grid: entry i owns the workgroups first[i] .. first[i + 1] - 1 (hrp_pack_weights_compact)
                 cdt = _cdt(self, dtype)
                 first = [0]
                 for w in group:
                     first.append(first[-1] + nv.lib().hrp_pack_blocks(w.cout, w.cin, w.ntaps, cdt, 1, 1 if w.need_t else 0))
-                fdev = torch.tensor(first, dtype=torch.int32, device=dev)
-                self.keep += [tdev, fdev]
+                fdev = torch.tensor(first, dtype=torch.int32, device=self.device)
+                self.keep.append(fdev)
                 dest.append((tdev, fdev, len(group), first[-1], cdt))
-        self._pack_stream = None
-        self._arena_clean = False      # the gradient arena was zeroed by this forward's run_prep (side stream)
-        if self._pack_tables_late:
-            self._pack_stream = torch.cuda.Stream(device=dev)
-            list.insert(self.fwd, cut, Entry(None, (), _PackJoin(self)))
-        self.merged = PLAN_MODE in ("merged", "hybrid")
-        if not self.merged:
-            self.wgrad_ws = {lane: torch.zeros(max(nb // 4, 4), dtype=torch.float32, device=dev)
-                             for lane, nb in self.wgrad_ws_bytes.items()}
-        # resolve deferred pointers (merged: the weight-gradient scratch is assigned below, once the batches are known)
-        for fn in self._late:
-            fn()
-        self._late = []
-        if FUSE_BN_REDUCE and self.need_grad:
-            self._fuse_bn_reduce()
+
+    def _print_stats(self):
+        import sys
+        msg = f"plan: {len(self.fwd)} forward / {len(self.bwd)} backward ops, {self.n_lanes} lanes, {self.counters}"
         if self.merged:
-            # lock-step merge of the virtual lanes into batched launches; streams only where a block asked for them
-            self.fwd_run, self.bwd_run = self._flatten(self.fwd), self._flatten(self.bwd)
-            if WGRAD_SINK > 1 and WGRAD_DEFER and BATCHING:
-                self.bwd_run = self._sink_wgrads(self.bwd_run)
             ops = [e.op for e in self.fwd_run + self.bwd_run if e.lane is not None]
-            batches = [op for op in ops if isinstance(op, BatchLaunch)]
-            wg_ops = [e for e in self.bwd_run if isinstance(e.op, (Launch, BatchLaunch)) and e.op.fam == "wgrad"]
-            defer = WGRAD_DEFER and bool(wg_ops)
-            # (descriptor.reserved == 1: a gradient some later launch of the list reads - folded on the spot)
-            now = {id(e.op) for e in wg_ops if any(it.desc.reserved for it in e.op.launches())}
-            if defer:
-                # deferred folds: every launch keeps its slabs until its lane folds them, so every problem gets its own
-                # scratch region (one bump allocation over the whole backward: ~4 GB for the benchmark network at B=64)
-                total, ws_off = 0, {}
-                for e in wg_ops:
-                    op = e.op
-                    for it in op.launches():
-                        it.desc.phase = 0 if id(op) in now else 1
-                    if isinstance(op, BatchLaunch):
-                        op.ws = op.ws_query()
-                    else:
-                        op_need = int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(op.desc)))
-                        op.desc.workspace_bytes = op_need
-                    sizes = op.ws if isinstance(op, BatchLaunch) else [op.desc.workspace_bytes]
-                    # (a batch that falls back to single launches: each item then wants its single-launch size)
-                    singles = [int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(it.desc))) for it in op.launches()]
-                    ws_off[id(op)] = []
-                    for b, b1 in zip(sizes, singles):
-                        ws_off[id(op)].append((total, max(b, b1)))
-                        total += _rup(max(b, b1), 256)
-                self.wgrad_ws = {0: torch.zeros(max(total // 4, 4), dtype=torch.float32, device=dev)}
-                base = self.wgrad_ws[0].data_ptr()
-                for e in wg_ops:
-                    for it, (off, b) in zip(e.op.launches(), ws_off[id(e.op)]):
-                        it.desc.workspace, it.desc.workspace_bytes = (base + off, b) if b else (None, 0)
-                for op in batches:
-                    op.prepare()
-                self.bwd_run = self._insert_folds(self.bwd_run)
-            else:
-                # weight-gradient scratch: one buffer per stream, every launch of that stream uses it in turn
-                need = {}
-                for e in self.fwd_run + self.bwd_run:
-                    op = e.op
-                    if isinstance(op, BatchLaunch) and op.fam == "wgrad":
-                        op.ws = op.ws_query()
-                        need[e.lane] = max(need.get(e.lane, 0), sum(_rup(b, 256) for b in op.ws))
-                    elif isinstance(op, Launch) and op.fam == "wgrad":
-                        need[e.lane] = max(need.get(e.lane, 0), int(nv.lib().hrp_wgrad_workspace_bytes(C.byref(op.desc))))
-                self.wgrad_ws = {lane: torch.zeros(max(nb // 4, 4), dtype=torch.float32, device=dev) for lane, nb in need.items()}
-                for e in self.fwd_run + self.bwd_run:
-                    op = e.op
-                    if isinstance(op, BatchLaunch) and op.fam == "wgrad":   # problems of one launch run concurrently: disjoint regions
-                        off = 0
-                        for it, b in zip(op.items, op.ws):
-                            it.desc.workspace, it.desc.workspace_bytes = self.wgrad_ws[e.lane].data_ptr() + off, b
-                            off += _rup(b, 256)
-                    elif isinstance(op, Launch) and op.fam == "wgrad":
-                        op.desc.workspace, op.desc.workspace_bytes = self.wgrad_ws[e.lane].data_ptr(), self.wgrad_ws[e.lane].numel() * 4
-                for op in batches:
-                    op.prepare()
-                    if op.fam == "wgrad" and op.singles:
-                        lane = next(e.lane for e in self.fwd_run + self.bwd_run if e.op is op)
-                        for it in op.items:
-                            it.desc.workspace, it.desc.workspace_bytes = self.wgrad_ws[lane].data_ptr(), self.wgrad_ws[lane].numel() * 4
-            used = {e.lane for e in self.fwd_run + self.bwd_run if e.lane is not None}
-            self._side_streams = [torch.cuda.Stream(device=dev) if (i + 1) in used else None for i in range(self.n_lanes - 1)]
-        else:
-            self._side_streams = [torch.cuda.Stream(device=dev) for _ in range(self.n_lanes - 1)]
-        self._bn_tables()
-        self.built = True
-        if PLAN_STATS:
-            import sys
-            msg = f"plan: {len(self.fwd)} forward / {len(self.bwd)} backward ops, {self.n_lanes} lanes, {self.counters}"
-            if self.merged:
-                ops = [e.op for e in self.fwd_run + self.bwd_run if e.lane is not None]
-                nb = sum(isinstance(op, BatchLaunch) and not op.singles for op in ops)
-                msg += (f"; {PLAN_MODE}: {sum(e.lane is not None for e in self.fwd_run)} / {sum(e.lane is not None for e in self.bwd_run)}"
-                        f" launches, {nb} of them batched, streams {sorted({e.lane for e in self.fwd_run if e.lane is not None})}")
-            print(msg, file=sys.stderr)
+            nb = sum(isinstance(op, BatchLaunch) and not op.singles for op in ops)
+            msg += (f"; {PLAN_MODE}: {sum(e.lane is not None for e in self.fwd_run)} / {sum(e.lane is not None for e in self.bwd_run)}"
+                    f" launches, {nb} of them batched, streams {sorted({e.lane for e in self.fwd_run if e.lane is not None})}")
+        print(msg, file=sys.stderr)
 
-
-    # ---- passes over the launch lists (plan_passes.py) -------------------------------------------------------------------
-    def _flatten(self, entries):
-        from . import plan_passes
-        return plan_passes.flatten(self, entries)
-
-    def _fuse_bn_reduce(self):
-        from . import plan_passes
-        return plan_passes.fuse_bn_reduce(self)
-
-    def _sink_wgrads(self, entries):
-        from . import plan_passes
-        return plan_passes.sink_wgrads(self, entries)
-
-    def _insert_folds(self, entries):
-        from . import plan_passes
-        return plan_passes.insert_folds(self, entries)
+    def upload(self, cobj, dtype=torch.uint8):
+        """A ctypes object (a table of descriptors or of numbers) as a device tensor of `dtype` that lives as long as the plan."""
+        t = torch.frombuffer(bytearray(bytes(cobj)), dtype=dtype).to(self.device)
+        self.keep.append(t)
+        return t
 
     def analyze_backward_split(self, min_frac=0.55, fracs=None):
-        from . import plan_passes
-        return plan_passes.analyze_backward_split(self, min_frac, fracs)
+        return passes.analyze_backward_split(self, min_frac, fracs)
 
     def _late_pack_cut(self):
         """Index in self.fwd right after the first parallel block (the join back into the main lane), or None when the
         plan is not a training plan with at least two parallel blocks and a network's worth of weights."""
         if not self.need_grad or len(self.weight_list) < 64:
             return None
-        joins = [i for i, e in enumerate(self.fwd) if e.lane is None and getattr(e.op, "kind", None) == "join"]
-        forks = [i for i, e in enumerate(self.fwd) if e.lane is None and getattr(e.op, "kind", None) == "fork"]
+        joins = [i for i, e in enumerate(self.fwd) if marker_kind(e) == "join"]
+        forks = [i for i, e in enumerate(self.fwd) if marker_kind(e) == "fork"]
         if len(forks) < 2 or not joins or forks[1] < joins[0]:
             return None           # (nested or single blocks: keep the simple order)
         return joins[0] + 1
@@ -868,9 +813,7 @@ class Plan:
         for i, e in enumerate(entries):
             for k, v in e.items():
                 setattr(tab[i], k, v)
-        tdev = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(self.device)
-        self.keep.append(tdev)
-        return tdev, len(entries)
+        return self.upload(tab), len(entries)
 
     def _bn_tables(self):
         self._run_tab = self._fold_tab = self._pgrad_tab = None
@@ -941,7 +884,7 @@ class Plan:
             late_s = self._pack_stream.cuda_stream
         for tdev, fdev, n, nblk, dt in self._pack_tables_late:
             nv.call("hrp_pack_weights_compact", tdev.data_ptr(), fdev.data_ptr(), n, nblk, dt, late_s)
-        if late_s != s and self.need_grad and self.grad_arena is not None and ARENA_ZERO_EARLY:
+        if late_s != s and self.need_grad and self.grad_arena is not None:
             # the gradient arena's memset (228 MB for the two-trunk network, 40 us) rides on the side stream under the stems instead of
             # standing between the loss and the backward, where nothing overlaps it; run_backward zeroes itself when this did not run
             with torch.cuda.stream(self._pack_stream):
@@ -1090,6 +1033,7 @@ class _Parallel:
 
 from .plan_blocks import BlockOps    # noqa: E402  (the mixins read this module's names at call time)
 from .plan_heads import HeadOps      # noqa: E402
+from . import plan_passes as passes  # noqa: E402  (Plan.finalize; the passes read this module's names at call time too)
 
 
 class PlanBuilder(BlockOps, HeadOps):
@@ -1292,8 +1236,7 @@ class PlanBuilder(BlockOps, HeadOps):
         for n_in, n_out in ((W, Wo), (H, Ho)):
             host = (C.c_int32 * (n_out * (nv.PIL_KMAX + 2)))()
             nv.check(nv.lib().hrp_pil_resize_table(n_in, n_out, host), "hrp_pil_resize_table")
-            tabs.append(torch.frombuffer(bytearray(bytes(host)), dtype=torch.int32).to(p.device))
-        p.keep += tabs
+            tabs.append(p.upload(host, torch.int32))
         m3, s3 = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
         dt = _dt(t.dtype)
 
@@ -1562,7 +1505,7 @@ class PlanBuilder(BlockOps, HeadOps):
                 e.a, e.b = sc.data_ptr(), sh.data_ptr()
             ins.append(e)
         vec = 16 // out.esz
-        if relu and out.requires_grad and RELU_BITMASK and Cc % vec == 0 and all(tm.t.pitch % vec == 0 for tm in terms):
+        if relu and out.requires_grad and Cc % vec == 0 and all(tm.t.pitch % vec == 0 for tm in terms):
             # the backward needs only the sign of the output: one byte per 16-byte vector instead of the tensor
             mask = torch.zeros(N * H * W * (Cc // vec), dtype=torch.uint8, device=p.device)
             p.keep.append(mask)

@@ -157,7 +157,7 @@ class BlockOps:
                 # the identity shortcut's gradient (out.grad under the block-end mask): nobody has written x.grad yet -> conv1's data
                 # gradient below adds it as a MASKED residual and writes x.grad once; else conv2's data gradient accumulates it as
                 # a second side output
-                masked_res = fd is not None and PL.MASKED_RES and not x.grad_written
+                masked_res = fd is not None and not x.grad_written
                 if fd is not None:
                     y2.take_grad_slot()
                 wg2_first = fd is None
@@ -183,7 +183,7 @@ class BlockOps:
                     # its reduce: in the epilogue of the launch that completes out.grad when that is a row-strip data gradient
                     # of this lane accumulating onto ONE earlier producer (the next block of the stack), else a pass of its own
                     nxt = p.row_last_writer.get(out.gptr())
-                    if (PL.BLOCK_END_REDUCE_FUSE and nxt is not None and not nxt[0].bnb_x and nxt[2] == len(out._grad_paths)
+                    if (nxt is not None and not nxt[0].bnb_x and nxt[2] == len(out._grad_paths)
                             and all(q == p.lane_path for q in out._grad_paths)):
                         gn = nxt[0]
                         gn.bnb_x, gn.bnb_x_pitch, gn.bnb_mask, gn.bnb_mask_pitch = y2.ptr(), y2.pitch, fd.mask, fd.mask_pitch

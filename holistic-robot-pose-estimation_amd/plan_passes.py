@@ -3,10 +3,11 @@
 flatten            lanes of the virtual parallel blocks walked in lock step, launches of one merge key folded into batched launches
 fuse_bn_reduce     BatchNorm-backward reduce passes moved into the epilogue of the data gradient that produces their input
 sink_wgrads        weight-gradient launches of a lane regrouped into batches of WGRAD_SINK problems
+assign_wgrad_scratch   where every weight-gradient problem keeps its partial slabs; prepares the batched launches
 insert_folds       one fold launch per WGRAD_FOLD_EVERY deferred weight-gradient problems
 analyze_backward_split   cut positions of the backward list after which a given share of the gradient bytes is final
 
-Every function takes the Plan as its first argument; the switches (BATCHING, GREEDY_MERGE, PLAN_MODE, WGRAD_SINK ..) are read from
+Every function takes the Plan as its first argument; the switches (BATCHING, PLAN_MODE, WGRAD_DEFER, WGRAD_SINK ..) are read from
 the plan module at call time, where tests and tools patch them."""
 import collections
 import ctypes as C
@@ -19,15 +20,15 @@ from . import plan as PL
 
 def flatten(plan, entries):
     """Launch list of the merged / hybrid modes.  The lanes of every VIRTUAL parallel block (all blocks in merged mode)
-    are walked in lock step - position k of every lane before position k + 1 of any - and launches of equal merge
-    key at one position are folded into batched launches.  Lanes of one block are independent by construction
+    are walked in lock step (`lockstep` below) and launches of equal merge key at the heads of their lanes are folded into
+    batched launches.  Lanes of one block are independent by construction
     (TensorH.check_readable / take_grad_slot), so any interleaving that keeps each lane's own order is a valid
     serial order.  Blocks that asked for streams (hybrid mode) keep their fork / join markers; the merge happens
     inside each of their lanes.  -> list of Entry (path unused)."""
     root = PL._Seq()
     for e in entries:
-        if e.lane is None and not isinstance(e.op, PL._PackJoin):
-            continue        # fork / join markers are re-created below
+        if PL.marker_kind(e) in ("fork", "join"):
+            continue        # re-created below (the pack join stays where it is)
         seq = root
         for blk, idx in (e.path or ()):
             node = seq.blocks.get(blk)
@@ -40,22 +41,17 @@ def flatten(plan, entries):
             # started and before it ended would otherwise be moved behind it
             assert seq.items[-1] is node, "plan: launches of a parallel block are interleaved with its parent's"
             seq = node.lanes.setdefault(idx, PL._Seq())
-        seq.items.append(e.op)
+        seq.items.append(e)
 
     def key_of(op):
-        return op.merge_key() if PL.BATCHING and isinstance(op, (PL.Launch, PL.BatchLaunch, PL.BlockLaunch)) else None
+        return op.merge_key() if PL.BATCHING and isinstance(op, PL.LaunchOp) else None
 
-    def emit_groups(groups, out):
-        for key, ops in groups.items():
-            if key[0] == "block":
-                out += PL._pair_block(plan, ops)
-            else:
-                out += ops if len(ops) == 1 else PL._merge_ops(plan, ops)
-
-    def greedy(kids):
-        """Lanes whose launch sequences differ (the paths of a fuse layer): instead of position k of every lane, take the
-        HEADS of all lanes, send the unbatchable ones out, then the largest group of equal merge key; the other lanes wait
-        for partners.  Any interleaving that keeps each lane's own order is valid."""
+    def lockstep(kids):
+        """The launch sequences of the lanes of one block -> one sequence.  Take the HEADS of all lanes, send the unbatchable ones
+        out, then the largest group of equal merge key; the other lanes wait for partners.  Lanes of equal sequences - the branches
+        of a module - so advance together, position k of every lane before position k + 1 of any; lanes whose sequences differ
+        (the paths of a fuse layer) find their partners where a walk by position would not: 646 -> 628 conv launches, 34.12 ->
+        33.87 ms per step (A/B/A/B on one box).  Any interleaving that keeps each lane's own order is valid."""
         out, ptr = [], [0] * len(kids)
         while True:
             heads = [(i, kids[i][ptr[i]]) for i in range(len(kids)) if ptr[i] < len(kids[i])]
@@ -73,38 +69,20 @@ def flatten(plan, entries):
             if moved:
                 continue
             key = max(groups, key=lambda k: len(groups[k]))
-            emit_groups({key: [op for _, op in groups[key]]}, out)
+            ops = [op for _, op in groups[key]]
+            if key[0] == "block":
+                out += PL._pair_block(plan, ops)
+            else:
+                out += ops if len(ops) == 1 else PL._merge_ops(plan, ops)
             for i, _ in groups[key]:
                 ptr[i] += 1
-
-    def lockstep(kids):
-        if PL.GREEDY_MERGE and len({tuple(key_of(op) for op in x) for x in kids}) > 1:
-            return greedy(kids)
-        out = []
-        for k in range(max(len(x) for x in kids)):
-            groups = collections.OrderedDict()
-            for x in kids:
-                if k < len(x):
-                    key = key_of(x[k])
-                    if key is None:
-                        out.append(x[k])
-                    else:
-                        groups.setdefault(key, []).append(x[k])
-            for key, ops in groups.items():
-                if key[0] == "block":
-                    out += PL._pair_block(plan, ops)
-                else:
-                    out += ops if len(ops) == 1 else PL._merge_ops(plan, ops)
-        return out
 
     def walk(seq, lane):
         """-> entries of this sequence, running on stream `lane`."""
         out = []
         for it in seq.items:
-            if isinstance(it, PL._PackJoin):
-                out.append(PL.Entry(None, (), it))
-            elif not isinstance(it, PL._Par):
-                out.append(PL.Entry(lane, (), it))
+            if not isinstance(it, PL._Par):
+                out.append(PL.Entry(None if it.lane is None else lane, (), it.op))
             else:
                 real = PL.PLAN_MODE == "hybrid" and plan._block_lanes.get(it.blk) is not None
                 if real:
@@ -127,17 +105,16 @@ def fuse_bn_reduce(plan):
     """conv -> BN -> ReLU -> conv (the interior of BasicBlock / Bottleneck, HRnet.py:41-57): the gradient of the
     activation comes from exactly one data-gradient launch; its epilogue then also accumulates the two BatchNorm
     backward sums (sum g, sum g * xhat) and the separate hrp_ew_bwd_reduce launch over the same tensors goes away."""
-    is_l = lambda e, fam: isinstance(e.op, PL.Launch) and e.op.fam == fam   # noqa: E731
     convs, other = {}, set()
     for i, e in enumerate(plan.bwd):
-        if is_l(e, "conv"):
+        if PL.is_fam(e.op, "conv"):
             convs.setdefault(e.op.desc.y, []).append((i, e))
-        elif is_l(e, "ew_app"):
+        elif PL.is_fam(e.op, "ew_app"):
             other.update(x for x in (e.op.desc.din, e.op.desc.din2) if x)
-    fwd_by_mask = {e.op.desc.mask: e.op for e in plan.fwd if is_l(e, "ew_fwd") and e.op.desc.mask}
+    fwd_by_mask = {e.op.desc.mask: e.op for e in plan.fwd if PL.is_fam(e.op, "ew_fwd") and e.op.desc.mask}
     drop = set()
     for i, e in enumerate(plan.bwd):
-        if not is_l(e, "ew_red"):
+        if not PL.is_fam(e.op, "ew_red"):
             continue
         b = e.op.desc
         if b.inp.mode != nv.EW_BN_TRAIN or b.inp.up != 1 or b.relu != 1 or not b.mask or b.dout in other:
@@ -179,6 +156,20 @@ def fuse_bn_reduce(plan):
     plan.counters["bn_reduce_fused"] = len(drop)
 
 
+def take_distinct(items, cap, keys_of):
+    """Stable partition: -> (up to `cap` items whose keys are pairwise distinct, the other items in their order - for the next
+    launch).  keys_of(item) -> the addresses the item writes."""
+    grp, rest, seen = [], [], set()
+    for it in items:
+        keys = keys_of(it)
+        if len(grp) < cap and seen.isdisjoint(keys):
+            grp.append(it)
+            seen.update(keys)
+        else:
+            rest.append(it)
+    return grp, rest
+
+
 def sink_wgrads(plan, entries):
     """Regroup the weight-gradient launches of every lane into batches of WGRAD_SINK problems of one tap count (their
     inputs - the layer's forward input and its output gradient - stay untouched for the rest of the step)."""
@@ -187,16 +178,8 @@ def sink_wgrads(plan, entries):
     def emit(lane, key, path, force):
         items = pend[lane][key]
         while items and (force or len(items) >= PL.WGRAD_SINK):
-            grp, rest, seen = [], [], set()
-            for it in items:
-                w = it.written()
-                if len(grp) < PL.WGRAD_SINK and not any(a in seen for a in w):
-                    grp.append(it)
-                    seen.update(w)
-                else:
-                    rest.append(it)
+            grp, items = take_distinct(items, PL.WGRAD_SINK, lambda it: it.written())
             out.append(PL.Entry(lane, path, grp[0] if len(grp) == 1 else PL.BatchLaunch(plan, grp)))
-            items = rest
         pend[lane][key] = items
 
     def flush(lane, path):
@@ -205,13 +188,13 @@ def sink_wgrads(plan, entries):
 
     for e in entries:
         if e.lane is None:
-            if getattr(e.op, "kind", None) == "join":
+            if PL.marker_kind(e) == "join":
                 for c in e.op.children:
                     flush(c, e.path)
             out.append(e)
             continue
         op = e.op
-        if isinstance(op, (PL.Launch, PL.BatchLaunch)) and op.fam == "wgrad" and not any(it.desc.reserved for it in op.launches()):
+        if PL.is_fam(op, "wgrad") and not any(it.desc.reserved for it in op.launches()):
             for it in op.launches():
                 key = it.merge_key()
                 if key is None:
@@ -227,6 +210,56 @@ def sink_wgrads(plan, entries):
     return out
 
 
+def assign_wgrad_scratch(plan):
+    """Where the weight-gradient launches of the merged backward list keep their partial slabs, then prepare() of every batched
+    launch of the plan (its table copies the descriptors: every pointer must be final).  -> True when the launches run in
+    phase 1 and wait for insert_folds.
+
+    WGRAD_DEFER: every launch keeps its slabs until its lane folds them, so every problem owns a region of ONE buffer - a bump
+    allocation over the whole backward (~4 GB for the benchmark network at B=64).  A launch with a `reserved` problem (a gradient
+    some later launch of the list reads) folds on the spot: phase 0.
+    Otherwise one buffer per stream, which the launches of that stream use in turn: the problems of a batched launch run
+    concurrently and lie side by side from the buffer's start; a launch on its own - also every item of a batch that prepare()
+    refused and that runs one by one - has the whole buffer."""
+    wg = [(e.lane, e.op) for e in plan.bwd_run if PL.is_fam(e.op, "wgrad")]
+    batches = [e.op for e in plan.fwd_run + plan.bwd_run if isinstance(e.op, PL.BatchLaunch)]
+    defer = PL.WGRAD_DEFER and bool(wg)
+    need, placed = {}, []          # buffer -> bytes; (op, buffer, [(offset, bytes)] or None: the whole buffer)
+    for lane, op in wg:
+        if defer:
+            phase = 0 if any(it.desc.reserved for it in op.launches()) else 1
+            for it in op.launches():
+                it.desc.phase = phase
+        sizes = op.ws_need(alone=defer)
+        if defer or isinstance(op, PL.BatchLaunch):
+            buf, off = (0, need.get(0, 0)) if defer else (lane, 0)
+            regions = []
+            for nbytes in sizes:
+                regions.append((off, nbytes))
+                off += PL._rup(nbytes, 256)
+        else:
+            buf, off, regions = lane, sizes[0], None
+        need[buf] = max(need.get(buf, 0), off)
+        placed.append((op, buf, regions))
+    plan.wgrad_ws = {buf: torch.zeros(max(nb // 4, 4), dtype=torch.float32, device=plan.device) for buf, nb in need.items()}
+
+    def point(op, buf, regions):
+        ws = plan.wgrad_ws[buf]
+        if regions is None:
+            regions = [(0, ws.numel() * 4)] * len(op.launches())
+        op.set_ws([(ws.data_ptr() + off, nbytes) if nbytes else (None, 0) for off, nbytes in regions])
+
+    for op, buf, regions in placed:
+        point(op, buf, regions)
+    for op in batches:
+        op.prepare()
+    if not defer:
+        for op, buf, regions in placed:
+            if regions is not None and op.singles:
+                point(op, buf, None)
+    return defer
+
+
 def insert_folds(plan, entries):
     """Deferred weight-gradient folds: after every WGRAD_FOLD_EVERY phase-1 problems of a lane, before the lane
     joins its parent and at the end of the list, one HRP_BATCH_WGRAD_FOLD launch folds the lane's pending slabs."""
@@ -237,27 +270,19 @@ def insert_folds(plan, entries):
         while descs and (everything or len(descs) >= nv.BATCH_MAX):
             # one launch folds problems with pairwise DISTINCT outputs only (the fold is a plain read-modify-write of dW:
             # a weight applied twice - or a tap group launched twice - must fold in consecutive launches, not race in one)
-            grp, rest, seen = [], [], set()
-            for f in descs:
-                key = f.dw + 4 * f.dw_tap_off
-                if len(grp) < nv.BATCH_MAX and key not in seen:
-                    grp.append(f)
-                    seen.add(key)
-                else:
-                    rest.append(f)
+            grp, descs = take_distinct(descs, nv.BATCH_MAX, lambda f: (f.dw + 4 * f.dw_tap_off,))
             b = PL.BatchLaunch(plan, [PL.Launch("wgrad_fold", f) for f in grp])
             b.prepare()
             out.append(PL.Entry(lane, path, b))
-            descs = rest
         if descs:
             pending[lane] = descs
 
     for e in entries:
-        if e.lane is None and getattr(e.op, "kind", None) == "join":
+        if PL.marker_kind(e) == "join":
             for c in e.op.children:
                 flush(c, e.path)
         out.append(e)
-        if e.lane is not None and isinstance(e.op, (PL.Launch, PL.BatchLaunch)) and e.op.fam == "wgrad" and e.op.launches()[0].desc.phase == 1:
+        if PL.is_fam(e.op, "wgrad") and e.op.launches()[0].desc.phase == 1:
             pending.setdefault(e.lane, []).extend(f for f in e.op.fold_descs() if f.G > 0)
             if len(pending[e.lane]) >= min(max(PL.WGRAD_FOLD_EVERY, 1), nv.BATCH_MAX):
                 flush(e.lane, e.path, everything=PL.WGRAD_FOLD_EVERY < nv.BATCH_MAX)
@@ -306,19 +331,19 @@ def analyze_backward_split(plan, min_frac=0.55, fracs=None):
         nv.call = lambda name, *args: [walk(a) for a in args] and 0
         depth, tops = 0, []
         for i, e in enumerate(plan.bwd_ops()):
-            lane, op = e.lane, e.op
-            if lane is None:
-                if getattr(op, "kind", None) == "fork":
+            op, kind = e.op, PL.marker_kind(e)
+            if e.lane is None:
+                if kind == "fork":
                     if depth == 0:
                         tops.append(i)
                     depth += 1
-                elif getattr(op, "kind", None) == "join":
+                elif kind == "join":
                     depth -= 1
                 continue
             if depth == 0:
                 tops.append(i)
             del hits[:]
-            if isinstance(op, (PL.Launch, PL.BatchLaunch, PL.BlockLaunch, PL.BlockBatch)):
+            if isinstance(op, PL.LaunchOp):
                 for it in op.launches():     # the descriptors say what a launch touches
                     walk(it.desc)
             else:

@@ -363,7 +363,7 @@ def test_plan_lockstep_merge_into_batched_launches():
     family / tap count at the same position fold into one batched launch, every lane keeps its own order, nested
     (virtual) blocks merge upwards, and two launches writing the same address never share a batch."""
     import torch
-    from hrpe_amd import plan as P
+    from hrpe_amd import plan as P, plan_passes as PP
     pl = P.Plan(torch.device("cpu"), torch.bfloat16, True, True)
     pb = P.PlanBuilder(pl)
     log = []
@@ -382,7 +382,7 @@ def test_plan_lockstep_merge_into_batched_launches():
     pl.fwd.append(P.Launch("conv", _fake_conv(0x5000000)))
     mode = P.PLAN_MODE
     P.PLAN_MODE = "merged"          # every block virtual: one stream
-    flat = [e.op for e in pl._flatten(pl.fwd)]
+    flat = [e.op for e in PP.flatten(pl, pl.fwd)]
     kinds = [type(op).__name__ if not callable(op) or isinstance(op, (P.Launch, P.BatchLaunch)) else "fn" for op in flat]
     # (the lanes' sequences differ - lane 2 has the nested block -, so they merge by their heads: the largest group first)
     assert kinds == ["fn", "BatchLaunch", "fn", "fn", "fn", "BatchLaunch", "Launch", "BatchLaunch", "Launch"], kinds
@@ -398,7 +398,7 @@ def test_plan_lockstep_merge_into_batched_launches():
             pl3.fwd.append(P.Launch("conv", _fake_conv(0x200000, ntaps=1)))
         with par.lane(1):
             pl3.fwd.append(P.Launch("conv", _fake_conv(0x300000, ntaps=1)))
-    ops3 = [e.op for e in pl3._flatten(pl3.fwd)]
+    ops3 = [e.op for e in PP.flatten(pl3, pl3.fwd)]
     assert [type(op).__name__ for op in ops3] == ["Launch", "BatchLaunch"] and ops3[0].desc.ntaps == 9 and len(ops3[1].items) == 2
     # the same output twice at one position: two launches, not one batch
     pl2 = P.Plan(torch.device("cpu"), torch.bfloat16, True, True)
@@ -407,11 +407,11 @@ def test_plan_lockstep_merge_into_batched_launches():
         for i in range(2):
             with par.lane(i):
                 pl2.fwd.append(P.Launch("conv", _fake_conv(0x100000)))
-    assert [type(e.op).__name__ for e in pl2._flatten(pl2.fwd)] == ["Launch", "Launch"]
+    assert [type(e.op).__name__ for e in PP.flatten(pl2, pl2.fwd)] == ["Launch", "Launch"]
     # batching off: the same order, one by one
     P.BATCHING = False
     try:
-        ops = [e.op for e in pl._flatten(pl.fwd)]
+        ops = [e.op for e in PP.flatten(pl, pl.fwd)]
         assert all(not isinstance(op, P.BatchLaunch) for op in ops) and len(ops) == 13
     finally:
         P.BATCHING = True
@@ -419,7 +419,7 @@ def test_plan_lockstep_merge_into_batched_launches():
     # virtual block inside lane 2 is merged
     P.PLAN_MODE = "hybrid"
     try:
-        ents = pl._flatten(pl.fwd)
+        ents = PP.flatten(pl, pl.fwd)
     finally:
         P.PLAN_MODE = mode
     marks = [getattr(e.op, "kind", None) for e in ents if e.lane is None]
@@ -445,10 +445,10 @@ def _fake_wgrad(dw, ntaps=9, cin=32, cout=32, hw=32, N=4):
 
 def test_plan_regroups_weight_gradients_and_defers_their_folds():
     """plan.py host logic of round 2: the weight-gradient launches of a lane are regrouped into batches of one tap count
-    wherever they sit (_sink_wgrads), run in phase 1 and are folded by HRP_BATCH_WGRAD_FOLD launches before the lane
-    joins / at the end (_insert_folds); a launch marked `reserved` (its gradient is read right away) stays put."""
+    wherever they sit (sink_wgrads), run in phase 1 and are folded by HRP_BATCH_WGRAD_FOLD launches before the lane
+    joins / at the end (insert_folds); a launch marked `reserved` (its gradient is read right away) stays put."""
     import torch
-    from hrpe_amd import plan as P
+    from hrpe_amd import plan as P, plan_passes as PP
     pl = P.Plan(torch.device("cpu"), torch.bfloat16, True, True)
     P.PlanBuilder(pl)
     log = []
@@ -462,7 +462,7 @@ def test_plan_regroups_weight_gradients_and_defers_their_folds():
     saved = P.WGRAD_SINK
     P.WGRAD_SINK = 3
     try:
-        out = pl._sink_wgrads(ents)
+        out = PP.sink_wgrads(pl, ents)
     finally:
         P.WGRAD_SINK = saved
     kinds = ["B%d" % len(e.op.items) if isinstance(e.op, P.BatchLaunch) else ("W" if isinstance(e.op, P.Launch) else "f") for e in out]
@@ -482,7 +482,7 @@ def test_plan_regroups_weight_gradients_and_defers_their_folds():
         if isinstance(e.op, P.BatchLaunch):
             e.op.prepare()
             assert e.op.info.grid2 == 0 and len(e.op.fold_descs()) == 3
-    folded = pl._insert_folds(out)
+    folded = PP.insert_folds(pl, out)
     fam = [e.op.fam if isinstance(e.op, (P.Launch, P.BatchLaunch)) else "f" for e in folded]
     assert fam[:-1] == ["f" if k == "f" else "wgrad" for k in kinds] and fam[-1] == "wgrad_fold"
     fold = folded[-1].op
@@ -517,10 +517,10 @@ def test_wgrad_fold_descriptor_and_refusals_are_host_only():
 
 
 def test_plan_folds_bn_backward_reduce_into_the_data_gradient():
-    """_fuse_bn_reduce (host logic): conv -> BN -> ReLU -> conv gives the data-gradient launch the BatchNorm operands
+    """plan_passes.fuse_bn_reduce (host logic): conv -> BN -> ReLU -> conv gives the data-gradient launch the BatchNorm operands
     and drops the reduce launch; an activation gradient with a second writer keeps its reduce pass."""
     import torch
-    from hrpe_amd import plan as P
+    from hrpe_amd import plan as P, plan_passes as PP
     pl = P.Plan(torch.device("cpu"), torch.bfloat16, True, True)
     P.PlanBuilder(pl)
 
@@ -553,7 +553,7 @@ def test_plan_folds_bn_backward_reduce_into_the_data_gradient():
     import types
     pl.grad_owner[0x1300000] = types.SimpleNamespace(_grad_paths=[()])
     pl.grad_owner[0x2300000] = types.SimpleNamespace(_grad_paths=[(), ()])
-    pl._fuse_bn_reduce()
+    PP.fuse_bn_reduce(pl)
     fams = [e.op.fam for e in pl.bwd]
     assert fams == ["ew_app", "conv", "ew_app", "conv", "ew_red", "ew_app"] and pl.counters["bn_reduce_fused"] == 1
     assert c1.bnb_x == 0x1200000 and c1.bnb_mask == 0x1100000 and c1.stats == 0x1400000 and c1.bnb_consts
