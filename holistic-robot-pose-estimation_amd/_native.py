@@ -332,6 +332,8 @@ PROTOTYPES = {
     "hrp_conv2d_fwd": [C.POINTER(ConvDesc), _P],
     "hrp_conv_rowstrip_channels": [C.POINTER(ConvDesc)],
     "hrp_conv_pointwise": [C.POINTER(ConvDesc)],
+    "hrp_conv_parity_fusable": [C.POINTER(ConvDesc)],
+    "hrp_conv_parity_fuse_enable": [_I],
     "hrp_conv_tile_config": [C.POINTER(ConvDesc)],
     "hrp_conv2d_bwd_weight": [C.POINTER(WgradDesc), _P],
     "hrp_colsum": [_P, _I, _L, _I, _I, _P, _I, _P, _L, _P],
@@ -362,6 +364,7 @@ PROTOTYPES = {
     "hrp_grad_accumulate": [_P, _P, _L, _I, _F, _P],
     "hrp_batch_prepare": [_I, _P, _I, _P, C.POINTER(BatchInfo)],
     "hrp_batch_launch": [_P, C.POINTER(BatchInfo), _P],
+    "hrp_batch_conv_parity_configs": [_P, C.POINTER(BatchInfo), _P],
     "hrp_softargmax_flat_fwd": [_P, _I, _I, _I, _I, _I, _P, _P, _P],
     "hrp_softargmax_flat_bwd": [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P],
     "hrp_rot6d_compose_fwd": [_P, _P, _P, _I, _P],

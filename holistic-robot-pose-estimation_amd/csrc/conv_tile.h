@@ -117,10 +117,19 @@ __device__ __forceinline__ void dma16(const char* src, char* lds_wave_base) {
 // stride; stat_slot: which of the HRP_STAT_SLOTS statistic replicas this workgroup adds into.  Called by the
 // single-problem kernel below with (blockIdx.x, gridDim.x) and by the batched kernel (conv_batch.h) with the block
 // index inside the problem it looked up.
-template <typename T, int CT, int PT, int WC, int WP, int NT, bool PERSIST, bool FAST>
+//
+// PF (parity-fused, conv_parity.h only): the data gradient of a 3x3 stride-2 layer as ONE tile program on the dy grid.  The nine
+// taps come class by class (pf_tap_class), each tap's product goes to the accumulator set of its output-parity class, and the
+// four class images leave as two dense row passes (py = 0, 1) of 2 * BM dx pixels each: [pixel][px][cout] in LDS, so that the
+// pixels 2b and 2b + 1 of a dx row are neighbours.  Only `res` of the epilogue fields is honoured.
+__host__ __device__ constexpr int pf_tap_class(int tap) { return tap < 1 ? 0 : tap < 3 ? 1 : tap < 5 ? 2 : 3; }
+
+template <typename T, int CT, int PT, int WC, int WP, int NT, bool PERSIST, bool FAST, bool PF = false>
 __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const ConvTiling& t, const int blk0,
                                                const int blk_stride, const int stat_slot) {
   static_assert(WC * WP == 4, "4 waves");
+  static_assert(!PF || (NT == 9 && Elem<T>::SZ == 2 && !PERSIST && FAST), "parity-fused: bf16, nine taps, one tile per workgroup");
+  constexpr int NCLS = PF ? 4 : 1, NPX = PF ? 2 : 1;   // accumulator sets; dx pixels per dy pixel in one epilogue pass
   constexpr int BN = 32 * CT * WC, BM = 32 * PT * WP;
   constexpr int SZ = Elem<T>::SZ, VEC = Elem<T>::VEC;
   constexpr int CKE = ROW / SZ;  // channels per chunk
@@ -207,7 +216,7 @@ __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const Con
   const int half_chunk = (d.Cin % CKE) ? nchunks - 1 : -1;    // chunk whose second 16 bytes lie beyond Cin
 
   // ---- store plan: the rows of the output tile this thread writes in the coalesced pass ----------------
-  constexpr int NV = BN / VEC, KST = BM * NV / 256;
+  constexpr int NV = BN / VEC, KST = NPX * BM * NV / 256;
   const int cv = tid % NV;  // 256 % NV == 0, so a thread keeps its channel group
   int out_rel[KST], out_code[KST];
   // The part of the setup that the first DMA stage does not need (fragment rows, store plan) runs after that stage
@@ -223,7 +232,8 @@ __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const Con
     }
 #pragma unroll
     for (int k = 0; k < KST; ++k) {
-      const int m = tid / NV + k * (256 / NV);
+      const int mi = tid / NV + k * (256 / NV);      // pixel of the LDS image; PF: (tile pixel, px)
+      const int m = PF ? mi >> 1 : mi;
       const int ti = fdiv16(m, t.fd_thw), rem = m - mul24(ti, thw);
       const int ty = fdiv16(rem, t.fd_tw), tx = rem - mul24(ty, t.TW);
       int code = (ti >= t.TI) ? 32 : 0;
@@ -231,7 +241,7 @@ __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const Con
       code |= (tx + x_last >= d.Wo) ? 8 : 0;
       code |= (ti + n_last >= d.N) ? 16 : 0;
       out_code[k] = code;
-      out_rel[k] = mul24(mul24(ti, d.y_H) + mul24(ty, d.out_stride), d.y_W) + mul24(tx, d.out_stride);   // in output pixels
+      out_rel[k] = mul24(mul24(ti, d.y_H) + mul24(ty, d.out_stride), d.y_W) + mul24(tx, d.out_stride) + (PF ? mi & 1 : 0);   // in output pixels
     }
   };
   bool first_tile = true;
@@ -265,9 +275,9 @@ __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const Con
     const char* xbase = xg + (((long long)n0 * d.H + iy0) * d.W + ix0) * (long long)d.x_pitch * SZ;
     const char* wbase = wg + (long long)co0 * ROW;
 
-    f32x16 acc[CT][PT];
+    f32x16 acc[NCLS * CT][PT];   // [class][c]: class 0 is the only one unless PF
 #pragma unroll
-    for (int c = 0; c < CT; ++c)
+    for (int c = 0; c < NCLS * CT; ++c)
 #pragma unroll
       for (int p = 0; p < PT; ++p)
 #pragma unroll
@@ -483,7 +493,7 @@ __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const Con
 #pragma unroll
           for (int c = 0; c < CT; ++c)
 #pragma unroll
-            for (int p = 0; p < PT; ++p) Mma<T>::mma(fa[cur][c], fb[cur][p], acc[c][p]);
+            for (int p = 0; p < PT; ++p) Mma<T>::mma(fa[cur][c], fb[cur][p], acc[(PF ? pf_tap_class(step) : 0) * CT + c][p]);
           if (more && (st + 1) * G + g < nloc) {
 #pragma unroll
             for (int u = 0; u < SPP; ++u) issue_slot(cbeg + (st + 1) * G + g, nbuf + g * t.buf_bytes, step * SPP + u);
@@ -503,6 +513,69 @@ __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const Con
     __syncthreads();
     HRP_CSTAMP(4);
 
+    if constexpr (PF) {
+      // ---- parity-fused epilogue: per row parity py of dx, the classes (py, 0) and (py, 1) -> LDS image [pixel][px][cout], then
+      // the coalesced pass with the residual.  The same roundings as the general epilogue below with `res` alone: bf16 image, fp32
+      // sum, bf16.  (A copy of its own and not one more mode of the code below: any edit there moves the register allocation of
+      // every other instance of this body.)
+      const int co = co0 + cv * VEC;
+      char* yg = (char*)d.y;
+      const char* rg = (const char*)d.res;
+#pragma unroll
+      for (int py = 0; py < 2; ++py) {
+        if (py) __syncthreads();      // the image of pass 0 has been read
+#pragma unroll
+        for (int c = 0; c < CT; ++c)
+#pragma unroll
+          for (int q4 = 0; q4 < 4; ++q4) {
+            const int cl = wc * 32 * CT + c * 32 + 8 * q4 + 4 * khalf;  // first of 4 consecutive local couts
+#pragma unroll
+            for (int p = 0; p < PT; ++p)
+#pragma unroll
+              for (int px = 0; px < 2; ++px) {
+                const int m = wp * (32 * PT) + p * 32 + l31;
+                const f32x16& a = acc[(2 * py + px) * CT + c][p];
+                uint2 r;
+                r.x = pack_bf2(a[4 * q4], a[4 * q4 + 1]);
+                r.y = pack_bf2(a[4 * q4 + 2], a[4 * q4 + 3]);
+                *(uint2*)(lds_out + (2 * m + px) * OP + cl * SZ) = r;
+              }
+          }
+        __syncthreads();
+        const long long ybase = ((long long)n0 * d.y_H + (oy0 * 2 + py)) * d.y_W + ox0 * 2;
+        if (co < d.Cout) {
+          const bool full = t.vec_ok && (co + VEC <= d.Cout);
+#pragma unroll
+          for (int k = 0; k < KST; ++k) {
+            if (out_code[k] & cls) continue;
+            const int mi = tid / NV + k * (256 / NV);
+            const size_t opix = (size_t)(ybase + out_rel[k]);
+            const uint4 raw = *(const uint4*)(lds_out + mi * OP + cv * 16);
+            if (full && !rg) {
+              *(uint4*)(yg + (opix * d.y_pitch + co) * SZ) = raw;
+            } else if (full) {
+              float f[VEC], r[VEC];
+              Elem<T>::unpack(raw, f);
+              Elem<T>::unpack(*(const uint4*)(rg + (opix * d.res_pitch + co) * SZ), r);
+#pragma unroll
+              for (int i = 0; i < VEC; ++i) f[i] += r[i];
+              *(uint4*)(yg + (opix * d.y_pitch + co) * SZ) = Elem<T>::pack(f);
+            } else {
+              float f[VEC];
+              Elem<T>::unpack(raw, f);
+#pragma unroll
+              for (int i = 0; i < VEC; ++i) {
+                if (co + i < d.Cout) {
+                  float val = f[i];
+                  if (rg) val += Elem<T>::ld(rg, opix * d.res_pitch + co + i);
+                  Elem<T>::st(yg, opix * d.y_pitch + co + i, val);
+                }
+              }
+            }
+          }
+        }
+      }
+    } else {
     // ---- epilogue: accumulators -> LDS tile [pixel][cout] (element type T) ----------------------
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
@@ -693,6 +766,7 @@ __device__ __forceinline__ void conv_tile_body(const hrp_conv_desc& d, const Con
         }
       }
     }
+    }   // (not PF)
     if constexpr (PERSIST) __syncthreads();   // the next tile's DMA overwrites the output image / statistics partials
     HRP_CSTAMP(7);
   }

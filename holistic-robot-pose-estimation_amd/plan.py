@@ -175,6 +175,10 @@ WGRAD_FOLD_EVERY = 32
 WGRAD_SINK = int(os.environ.get("HRP_WGRAD_SINK", "16"))
 # stride-2 data gradients: parity classes padded to 4 taps (PlanBuilder._conv_bwd)
 PARITY_PAD = True
+# ... and the four parity classes of a 3x3 layer share ONE batched launch whatever their tap counts, cut at whole layers only: the
+# library then runs each layer as one nine-tap problem on the dy grid (csrc/conv_parity.h, hrp_conv_parity_fusable).  Off: one
+# batched launch per tap count, as before.
+PARITY_FUSE = os.environ.get("HRP_PARITY_FUSE", "1") not in ("0", "")
 # train-mode BasicBlock interiors conv -> BN -> ReLU -> conv on the row-strip kernel (csrc/conv_row.h): the BatchNorm + ReLU
 # runs in the second convolution's staging path, its backward in the staging path of the first convolution's data gradient
 ROWCONV_FUSE = True
@@ -201,8 +205,8 @@ DBG_SYNC = os.environ.get("HRP_DBG_SYNC")                 # development aid: dev
 # The switches above without an environment variable - MAX_LANE_DEPTH, BATCHING, WGRAD_DEFER, WGRAD_FOLD_EVERY, PARITY_PAD,
 # ROWCONV_FUSE, BLOCK_END_FUSE - are module constants: tests and tools patch them (plan.X = ...) before a plan is built and use the
 # other setting as their reference.  The environment variables are for a user of the library or of bench.py:
-# HRP_PLAN_MODE, HRP_SERIAL_LANES, HRP_WGRAD_SINK, HRP_BLOCK_FUSE, HRP_BLOCK_END_FWD, HRP_TAIL_FUSE, HRP_POOL_FUSE, HRP_LAZY_INPUTS,
-# HRP_PLAN_STATS, HRP_DBG_SYNC.
+# HRP_PLAN_MODE, HRP_SERIAL_LANES, HRP_WGRAD_SINK, HRP_PARITY_FUSE, HRP_BLOCK_FUSE, HRP_BLOCK_END_FWD, HRP_TAIL_FUSE, HRP_POOL_FUSE,
+# HRP_LAZY_INPUTS, HRP_PLAN_STATS, HRP_DBG_SYNC.
 
 # largest dilation of a 3x3 convolution the tile program runs as ONE problem (its halo tile must fit LDS); beyond it
 # PlanBuilder._conv_shifted_taps splits the taps into one-tap problems
@@ -239,6 +243,8 @@ FAMILIES = {"conv": (nv.BATCH_CONV, "hrp_conv2d_fwd", nv.ConvDesc),
             "ew_red": (nv.BATCH_EW_BWD_REDUCE, "hrp_ew_bwd_reduce", nv.EwBwdDesc),
             "ew_app": (nv.BATCH_EW_BWD_APPLY, "hrp_ew_bwd_apply", nv.EwBwdDesc),
             "wgrad_fold": (nv.BATCH_WGRAD_FOLD, None, nv.WgradFoldDesc)}
+# merge key of the parity-class problems of the 3x3 stride-2 data gradients (PARITY_FUSE): in place of their tap count
+PARITY_KEY = ("conv", nv.HRP_BF16, "parity")
 
 
 class LaunchOp:
@@ -301,6 +307,8 @@ class Launch(LaunchOp):
                 return None
             if d.ntaps == 1 and nv.lib().hrp_conv_pointwise(C.byref(d)):
                 return None      # the pointwise kernel (csrc/conv_pw.h) exists as a single launch only
+            if PARITY_FUSE and d.out_stride == 2 and nv.lib().hrp_conv_parity_fusable(C.byref(d)):
+                return PARITY_KEY      # the four classes of a layer, 1 / 2 / 2 / 4 or 4 / 4 / 4 / 4 taps: one fused problem
             return ("conv", d.dtype, d.ntaps)
         if self.fam == "wgrad":
             return ("wgrad", d.dtype, d.ntaps, d.reserved)
@@ -353,6 +361,8 @@ class BatchLaunch(LaunchOp):
         info = nv.BatchInfo()
         nbytes = int(nv.lib().hrp_batch_table_bytes(famid, n))
         host = (C.c_char * nbytes)()
+        # (PARITY_FUSE off: also the padded classes, four problems of one tap count whatever the merge key, stay class problems)
+        fuse = nv.lib().hrp_conv_parity_fuse_enable(1 if PARITY_FUSE else 0)
         try:
             nv.check(nv.lib().hrp_batch_prepare(famid, arr, n, host, C.byref(info)), "hrp_batch_prepare")
         except nv.HrpError:
@@ -363,6 +373,8 @@ class BatchLaunch(LaunchOp):
                 print(f"plan: batch of {n} {self.fam} launches runs one by one ({nv.lib().hrp_last_error().decode()})", file=sys.stderr)
             self.singles = True      # not batchable after all (scalar path, tile does not fit ..): one by one
             return
+        finally:
+            nv.lib().hrp_conv_parity_fuse_enable(fuse)
         self.info = info
         if self.fam == "wgrad" and self.items[0].desc.phase == 1:
             folds = (nv.WgradFoldDesc * n)()
@@ -446,13 +458,17 @@ def _merge_ops(plan, ops):
     """Ops of equal merge key -> batched launches of at most BATCH_MAX problems with pairwise distinct outputs."""
     # (not plan_passes.take_distinct, a stable partition: here a conflict closes the running group and nothing is carried past it)
     items = [l for op in ops for l in op.launches()]
+    # the parity classes of a layer arrive side by side (the lanes of their virtual block) and stay in one launch: the fused kernel
+    # takes complete quadruples only, so a batch of them is cut between layers
+    step = 4 if ops[0].merge_key() == PARITY_KEY and len(items) % 4 == 0 else 1
     out, cur, seen = [], [], set()
-    for it in items:
-        w = it.written()
-        if len(cur) == nv.BATCH_MAX or any(a in seen for a in w):
+    for i in range(0, len(items), step):
+        unit = items[i:i + step]
+        w = [a for it in unit for a in it.written()]
+        if len(cur) + step > nv.BATCH_MAX or any(a in seen for a in w):
             out.append(cur)
             cur, seen = [], set()
-        cur.append(it)
+        cur += unit
         seen.update(w)
     out.append(cur)
     return [g[0] if len(g) == 1 else BatchLaunch(plan, g) for g in out]
@@ -1416,7 +1432,8 @@ class PlanBuilder(BlockOps, HeadOps):
             geos = [G.data_grad_s1(x.H, x.W, ksize, dilation)] if stride == 1 else G.data_grad_s2(x.H, x.W, ksize, pad4)
             # (without a residual res_pitch stays 0 here, unlike in the forward descriptors)
             res = (x.gptr(), x.pitch) if acc else (None, 0)
-            # stride 2: the parity classes write disjoint pixels: virtual lanes (the class index), one batched launch per tap count
+            # stride 2: the parity classes write disjoint pixels: virtual lanes (the class index), one batched launch per tap count -
+            # or, for the 3x3 layers under PARITY_FUSE, one launch for the four of them, which the library runs as one problem
             with self.parallel(4, virtual=True) if stride == 2 else contextlib.nullcontext() as par:
                 for geo in geos:
                     d = self._conv_desc(geo, y.operand(grad=True), x.operand(grad=True), dtype, res=res)

@@ -417,6 +417,17 @@ int hrp_conv_rowstrip_channels(const hrp_conv_desc* d);
  * 256 input channels and >= 131 072 output pixels - the Bottleneck 1x1 layers at 64 x 64, HRnet.py:60-98), else 0.  Such a
  * problem placed in a HRP_BATCH_CONV launch runs the general tile program: callers launch it on its own.  Host only. */
 int hrp_conv_pointwise(const hrp_conv_desc* d);
+/* 1 when d is one output-parity class of the data gradient of a 3x3 stride-2 padding-1 layer in the form the parity-fused kernel
+ * (csrc/conv_parity.h) takes: bf16, in_stride 1, out_stride 2, offsets in {0, 1}^2, y_H = 2 Ho and y_W = 2 Wo, the class's 1 / 2 /
+ * 2 / 4 taps on slots of a 9- or 10-slot packing (further taps, up to four, must read the zero slot 9), Cin a multiple of 16, Cout
+ * of 8, 16-byte pitches, nothing of the epilogue set but `res`.  A HRP_BATCH_CONV prepare whose n problems are the four classes of
+ * n / 4 layers (equal x, w, y, res and shapes; any order, any mix of padded and unpadded tap counts) runs one fused problem per
+ * layer; any other batch takes the ordinary path.  Reads no pointer.  Host only. */
+int hrp_conv_parity_fusable(const hrp_conv_desc* d);
+/* Process-wide switch of that grouping, on by default: 0 makes every later HRP_BATCH_CONV prepare take the ordinary path, also for
+ * complete quadruples (four padded 4-tap problems share one launch of the ordinary kernel) - the reference side of an A/B
+ * measurement in one process.  -> the previous setting. */
+int hrp_conv_parity_fuse_enable(int on);
 /* CT * 1000 + PT * 100 + WC * 10 + WP - the tile configuration (csrc/conv_tile.h: 32 CT WC output channels x 32 PT WP pixels per
  * workgroup, WC x WP waves) - when hrp_conv2d_fwd will run problem d on the general tile program, + 10000 when that launch splits K
  * (two workgroups per output tile, fp32 atomics): 2214, 2114, 1122, 1214 or 1114.  0 when d runs on the row-strip or the pointwise
@@ -507,7 +518,8 @@ int hrp_ew_bwd_apply(const hrp_ew_bwd_desc* d, void* stream);
  * range(self.num_branches): x[i] = self.branches[i](x[i])`) and its two trunks one after the other
  * (full_net.py:252-302); they are independent until the fuse layers / the heads, so the same layer of every branch
  * of both trunks is one launch here.  Problems may differ in shape (each gets its own tile configuration inside
- * the launch) but share the family, the element type and - convolutions, weight gradients - the tap count.
+ * the launch) but share the family, the element type and - convolutions, weight gradients - the tap count (but for the parity
+ * classes of 3x3 stride-2 data gradients, which may mix 1 / 2 / 4 taps when every layer is complete: hrp_conv_parity_fusable).
  *
  *   hrp_batch_prepare  host only (no HIP call): validates the n descriptors, chooses tiles, fills `info` and, when
  *                      table_host != NULL, the launch table (hrp_batch_table_bytes(family, n) bytes of HOST memory).
@@ -536,6 +548,10 @@ typedef struct hrp_batch_info {
 int64_t hrp_batch_table_bytes(int family, int n);
 int hrp_batch_prepare(int family, const void* descs, int n, void* table_host, hrp_batch_info* info);
 int hrp_batch_launch(const void* table_dev, const hrp_batch_info* info, void* stream);
+/* Parity-fused HRP_BATCH_CONV launch (hrp_conv_parity_fusable): -> the number of fused problems, n / 4, and in out[0 .. n / 4) the
+ * tile configuration of each in table order, CT * 1000 + PT * 100 + 14 as hrp_conv_tile_config reports it (1214, 1114 or 2114):
+ * problem i owns the blocks blk0[i] .. blk0[i + 1].  0 for a prepared conv batch that took the ordinary path.  Host only. */
+int hrp_batch_conv_parity_configs(const void* table_host, const hrp_batch_info* info, int32_t* out);
 /* fold descriptors of a phase-1 weight-gradient launch: of a single launch (the tiling hrp_conv2d_bwd_weight will
  * choose for d) / of the n problems of a prepared HRP_BATCH_WGRAD table (host copy), in the CALLER's order */
 int hrp_wgrad_fold_desc_of(const hrp_wgrad_desc* d, hrp_wgrad_fold_desc* out);
