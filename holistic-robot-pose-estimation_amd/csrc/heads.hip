@@ -704,7 +704,8 @@ extern "C" int hrp_softargmax_flat_fwd(const void* logits, int dtype, int B, int
 
 extern "C" int hrp_softargmax_flat_bwd(const void* logits, int dtype, int B, int J, int HW, int pitch, const float* coord,
                                        const float* ms, const float* dcoord, void* dlogits, int dpitch, void* stream) {
-  HRP_REQUIRE(logits && coord && ms && dcoord && dlogits && B > 0 && J > 0 && HW > 0, "softargmax_flat_bwd: bad args");
+  HRP_REQUIRE(logits && coord && ms && dcoord && dlogits && B > 0 && J > 0 && HW > 0 && pitch >= J && dpitch >= J,
+              "softargmax_flat_bwd: bad args");
   if (dtype == HRP_F32) hipLaunchKernelGGL(softargmax_flat_bwd_kernel<float>, dim3(J, B), dim3(64), 0, (hipStream_t)stream, logits, HW, pitch, coord, ms, dcoord, dlogits, dpitch);
   else hipLaunchKernelGGL(softargmax_flat_bwd_kernel<bf16_t>, dim3(J, B), dim3(64), 0, (hipStream_t)stream, logits, HW, pitch, coord, ms, dcoord, dlogits, dpitch);
   return check_launch("softargmax_flat_bwd");
@@ -725,9 +726,11 @@ extern "C" int hrp_softargmax3d_fwd(const void* logits, int dtype, int B, int J,
 extern "C" int hrp_softargmax3d_bwd(const void* logits, int dtype, int B, int J, int D, int H, int W, int pitch,
                                     int root, int fix_root, const float* uvd, const float* ms, const float* duvd,
                                     void* dlogits, int dpitch, void* stream) {
-  HRP_REQUIRE(logits && uvd && ms && duvd && dlogits, "softargmax_bwd: bad args");
+  HRP_REQUIRE(logits && uvd && ms && duvd && dlogits && B > 0 && J > 0, "softargmax_bwd: bad args");
   const int vec = dtype == HRP_F32 ? 4 : 8;
-  HRP_REQUIRE(D % vec == 0 && pitch % vec == 0 && dpitch % vec == 0, "softargmax_bwd: alignment");
+  HRP_REQUIRE(D % vec == 0 && D / vec <= 256 && 256 % (D / vec) == 0, "softargmax_bwd: D=%d unsupported", D);
+  HRP_REQUIRE(pitch % vec == 0 && dpitch % vec == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)dlogits % 16 == 0,
+              "softargmax_bwd: alignment");
   long total = (long)H * W * (J * D / vec);
   int gx = (int)((total + 255) / 256);
   if (gx > 64) gx = 64;
