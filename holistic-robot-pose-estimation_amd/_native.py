@@ -300,6 +300,9 @@ TRACK_NO_ESTIMATE, TRACK_BAD_BOX, TRACK_LOST_OUT = 1, 2, 4             # HRP_TRA
 TRACK_BBOX_EXTENDED, TRACK_BBOX_ORIGIN, TRACK_BBOX_STRICT = 0, 1, 2    # HRP_TRACK_BBOX_*
 TRACK_MAX_KP, TRACK_MAX_SIZE = 32, 4096
 SEED_SKIPPED, SEED_TAKEN, SEED_REFUSED = 1, 2, 4                        # HRP_SEED_*
+VERIFY_SKIPPED, VERIFY_KEPT, VERIFY_UNDECIDED, VERIFY_DROPPED = 1, 2, 4, 8    # HRP_VERIFY_*
+VERIFY_FAIL_SUPPORT, VERIFY_FAIL_COVERAGE, VERIFY_FAIL_IOU = 16, 32, 64
+TRACK_MAX_BONES, TRACK_MAX_SAMPLES = 32, 64
 KP_STRIP_ROWS = 1                                                       # HRP_KP_STRIP_ROWS: input rows per workgroup of hrp_kp_readout_fwd
 
 
@@ -307,6 +310,14 @@ class TrackGeom(C.Structure):     # hrp_track_geom
     _fields_ = [("status", C.c_int32), ("crop_x0", C.c_int32), ("crop_y0", C.c_int32), ("crop_x1", C.c_int32), ("crop_y1", C.c_int32),
                 ("side", C.c_int32), ("off_x", C.c_int32), ("off_y", C.c_int32), ("bbox_strict_bounded", (C.c_float * 4) * 2),
                 ("bbox_gt2d_extended", (C.c_float * 4) * 2), ("bbox_strict_bounded_original", C.c_float * 4)]
+
+
+class TrackVerifyDesc(C.Structure):     # hrp_track_verify_desc
+    _fields_ = [(n, C.c_void_p) for n in ("state_kp2d", "state_have", "mask", "alpha", "verify_status", "counts", "sums")] + \
+               [(n, C.c_int32) for n in ("B", "nkp", "hm", "wm", "nb", "samples", "min_fg", "min_samples")] + \
+               [("bones", (C.c_int32 * 2) * TRACK_MAX_BONES), ("scale", C.c_double * 2), ("extend_ratio", C.c_double * 2),
+                ("min_support", C.c_double), ("min_coverage", C.c_double), ("min_iou", C.c_double), ("min_prob", C.c_float),
+                ("reserved", C.c_int32)]
 
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
@@ -409,6 +420,7 @@ PROTOTYPES = {
     "hrp_track_prepare": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P],
     "hrp_track_update": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "hrp_track_seed": [_P, _I, _I, C.POINTER(C.c_double), _P, _I, _I, _F, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
+    "hrp_track_verify": [C.POINTER(TrackVerifyDesc), _P],
     "hrp_kp_readout_pack": [_P, _I, _I, _P, _I, _P],
     "hrp_kp_readout_ws": [_I, _I],                    # returns int64 (set in lib())
     "hrp_kp_readout_fwd": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _L, _P],

@@ -372,4 +372,125 @@ TRK_HD int track_seed(const float* det, int nkp, double inv_sx, double inv_sy, c
   return HRP_SEED_TAKEN;
 }
 
+// ---- verification: the estimate against the detector's foreground map ----------------------------------------------------------
+// The rule of include/hrp.h (hrp_track_verify) in the pieces the kernel shares out among its lanes: verify_geometry once per
+// stream, verify_sample per sample point, verify_pixel per pixel, verify_decide once on the totals.  track_verify below is the
+// same rule for one stream in one thread (tests/track_verify_host_check.cpp); only the order of the float64 sums differs.
+struct VerifyGeom {
+  double d[HRP_TRACK_MAX_KP][2];     // the key-points in detector pixels
+  double box[4];                     // the extended box of step 4
+};
+struct VerifyAcc {
+  double I, S, R;
+  int n_fg, n_in;
+};
+
+// steps 0 - 2 and the box: 0 to go on, otherwise the stream's final status (HRP_VERIFY_SKIPPED, or HRP_VERIFY_DROPPED)
+TRK_HD int verify_geometry(const double* kp2d, int nkp, int have, double sx, double sy, double er0, double er1, VerifyGeom& g) {
+  if (!have) return HRP_VERIFY_SKIPPED;
+  double x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+  for (int i = 0; i < nkp; ++i) {
+    const double u = kp2d[2 * i], v = kp2d[2 * i + 1];
+    const double x = u * sx, y = v * sy;
+    if (!finite64(u) || !finite64(v) || !finite64(x) || !finite64(y)) return HRP_VERIFY_DROPPED;
+    g.d[i][0] = x;
+    g.d[i][1] = y;
+    if (i == 0) {
+      x0 = x1 = x;
+      y0 = y1 = y;
+    } else {
+      x0 = x < x0 ? x : x0;
+      y0 = y < y0 ? y : y0;
+      x1 = x > x1 ? x : x1;
+      y1 = y > y1 ? y : y1;
+    }
+  }
+  const double w = x1 - x0, h = y1 - y0;
+  g.box[0] = x0 - er0 * w;
+  g.box[1] = y0 - er1 * h;
+  g.box[2] = x1 + er0 * w;
+  g.box[3] = y1 + er1 * h;
+  return 0;
+}
+
+TRK_HD int verify_samples(int nkp, int nb, int S) { return nkp + nb * S; }
+
+// sample s of nkp + nb * S: the key-points first, then S points along every bone.  The mask index is formed only from values
+// already tested against [0, wm) x [0, hm) in double, and tested again as integers before the load.
+TRK_HD void verify_sample(const VerifyGeom& g, int nkp, const int32_t (*bones)[2], int S, int s, const float* mask, int hm, int wm,
+                          float min_prob, int& counted, int& hit) {
+  double x, y;
+  if (s < nkp) {
+    x = g.d[s][0];
+    y = g.d[s][1];
+  } else {
+    const int k = (s - nkp) / S, j = (s - nkp) % S;
+    const int a = bones[k][0], b = bones[k][1];
+    if (a < 0 || a >= nkp || b < 0 || b >= nkp) return;      // (the entry point refuses such a bone)
+    const double t = ((double)j + 0.5) / (double)S;
+    x = g.d[a][0] + t * (g.d[b][0] - g.d[a][0]);
+    y = g.d[a][1] + t * (g.d[b][1] - g.d[a][1]);
+  }
+  if (!(x >= 0.0 && x < (double)wm && y >= 0.0 && y < (double)hm)) return;
+  const int ix = (int)x, iy = (int)y;
+  if (ix < 0 || ix >= wm || iy < 0 || iy >= hm) return;
+  ++counted;
+  if (mask[(int64_t)iy * wm + ix] >= min_prob) ++hit;
+}
+
+// pixel (x, y) with mask value m and silhouette value a (read only when use_alpha)
+TRK_HD void verify_pixel(const VerifyGeom& g, float m, float a, bool use_alpha, int x, int y, float min_prob, VerifyAcc& acc) {
+  const double md = (double)m;
+  acc.S += md;
+  if (use_alpha) {
+    const double ad = (double)a;
+    acc.R += ad;
+    acc.I += md * ad;
+  }
+  if (m >= min_prob) {
+    ++acc.n_fg;
+    const double cx = (double)x + 0.5, cy = (double)y + 0.5;
+    if (cx >= g.box[0] && cx <= g.box[2] && cy >= g.box[1] && cy <= g.box[3]) ++acc.n_in;
+  }
+}
+
+// step 6 on the totals; have is written only when the stream is dropped
+TRK_HD int verify_decide(int h_s, int n_s, int n_in, int n_fg, double I, double S, double R, bool use_alpha, int min_fg,
+                         int min_samples, double min_support, double min_coverage, double min_iou, int32_t& have) {
+  if (n_fg < min_fg) return HRP_VERIFY_UNDECIDED;
+  int fail = 0;
+  if (min_support >= 0.0 && n_s >= min_samples && !((double)h_s / (double)n_s >= min_support)) fail |= HRP_VERIFY_FAIL_SUPPORT;
+  if (min_coverage >= 0.0 && !((double)n_in / (double)n_fg >= min_coverage)) fail |= HRP_VERIFY_FAIL_COVERAGE;
+  if (min_iou >= 0.0 && use_alpha && !(I / (S + R - I) >= min_iou)) fail |= HRP_VERIFY_FAIL_IOU;
+  if (!fail) return HRP_VERIFY_KEPT;
+  have = 0;
+  return HRP_VERIFY_DROPPED | fail;
+}
+
+// One stream in one thread.  state [nkp][2] float64 is only read; counts [4] = (h_s, n_s, n_in, n_fg), sums [3] = (I, S, R).
+TRK_HD int track_verify(const double* state, int nkp, int32_t& have, double sx, double sy, const float* mask, const float* alpha,
+                        int hm, int wm, const int32_t (*bones)[2], int nb, int S, double er0, double er1, float min_prob, int min_fg,
+                        int min_samples, double min_support, double min_coverage, double min_iou, int32_t* counts, double* sums) {
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  sums[0] = sums[1] = sums[2] = 0.0;
+  VerifyGeom g;
+  const int early = verify_geometry(state, nkp, have, sx, sy, er0, er1, g);
+  if (early) {
+    if (early == HRP_VERIFY_DROPPED) have = 0;
+    return early;
+  }
+  int counted = 0, hit = 0;
+  for (int s = 0; s < verify_samples(nkp, nb, S); ++s) verify_sample(g, nkp, bones, S, s, mask, hm, wm, min_prob, counted, hit);
+  VerifyAcc acc = {0.0, 0.0, 0.0, 0, 0};
+  for (int y = 0; y < hm; ++y)
+    for (int x = 0; x < wm; ++x) {
+      const int64_t i = (int64_t)y * wm + x;
+      verify_pixel(g, mask[i], alpha ? alpha[i] : 0.f, alpha != nullptr, x, y, min_prob, acc);
+    }
+  counts[0] = hit, counts[1] = counted, counts[2] = acc.n_in, counts[3] = acc.n_fg;
+  sums[0] = acc.I, sums[1] = acc.S, sums[2] = acc.R;
+  return verify_decide(hit, counted, acc.n_in, acc.n_fg, acc.I, acc.S, acc.R, alpha != nullptr, min_fg, min_samples, min_support,
+                       min_coverage, min_iou, have);
+}
+
 }  // namespace track

@@ -15,7 +15,8 @@ reused, so ``prepare`` and ``update`` can be captured in a graph.  A stream with
 would refuse, a prediction behind the camera or outside the frame) takes the whole frame and says so in ``status``; it recovers
 as soon as a prediction is usable again, or - the networks were trained on tight crops - at the next ACQUISITION: ``acquire`` runs a
 full-frame detector (CtRNet's ``seg_mask_inference.detect``) and one launch (``hrp_track_seed``) makes its key-points the estimate of
-the streams that have none; ``step`` schedules it every ``acquire_every`` frames.  ``process_truncation`` is not part of the tracker: it crops inside the frame.  There is
+the streams that have none; ``step`` schedules it every ``acquire_every`` frames.  With ``min_support`` / ``min_coverage`` /
+``min_iou`` one more launch in between (``hrp_track_verify``) drops the estimate of a stream that the detector's mask contradicts.  ``process_truncation`` is not part of the tracker: it crops inside the frame.  There is
 no CPU path: CPU tensors raise HrpError."""
 import ctypes as C
 from collections import namedtuple
@@ -33,7 +34,8 @@ class PoseTracker:
 
     def __init__(self, model, robot, K_original, frame_hw, streams=1, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256),
                  extend_ratio=(0.2, 0.13), use_origin_bbox=False, use_extended_bbox=True, reference_keypoint_id=3, min_inside=1,
-                 device=None, detector=None, detector_scale=0.5, acquire_every=0):
+                 device=None, detector=None, detector_scale=0.5, acquire_every=0, min_support=None, min_coverage=None, min_iou=None,
+                 bones=None, verify_samples=16, verify_min_fg=16, verify_min_samples=4, verify_min_prob=0.5, renderer=None):
         """model: a callable with RootNetwithRegInt.forward's signature returning its tuple (xyz_fk last); a module is put in
         eval().  robot: its ``nkp`` (or ``link_names``) gives the number of key-points.  K_original: [3, 3] or [streams, 3, 3].
         frame_hw: (H, W) of every frame.  The bbox options select the box and K of ``k_values`` as prepare_batch does
@@ -42,13 +44,44 @@ class PoseTracker:
         detector: a callable uint8 [B, 3, H, W] -> (key-points [B, nkp, 2] fp32 in ITS pixels, foreground probability [B, 1, h, w] /
         [B, h, w] or None, ms [B, nkp, 2] or None), e.g. ``seg_mask_inference.detect``; detector_scale: detector pixels per frame
         pixel (a number or (x, y); seg_mask_inference's ``scale``); acquire_every: ``step`` runs ``acquire`` on every
-        acquire_every-th frame (0: never)."""
+        acquire_every-th frame (0: never).
+        min_support / min_coverage / min_iou: thresholds in [0, 1] of the verification that ``acquire`` runs between the detector
+        and ``seed`` (``verify``, include/hrp.h hrp_track_verify); verification is on when any of them is given.  bones: key-point
+        index pairs the support samples lie along (default: the serial chain (i, i + 1) for panda and kuka, none otherwise);
+        verify_samples per bone; verify_min_fg foreground pixels below which the detector is taken to see no robot;
+        verify_min_samples support samples inside the map below which support is not applied; verify_min_prob the foreground
+        probability.  renderer: a RobotMeshRenderer at the detector's resolution (``robot.set_robot_renderer(K_original, frame_hw,
+        scale=detector_scale)``), needed by min_iou and only by it: the silhouette of the last prediction is rendered on
+        acquisition frames."""
         ds = tuple(detector_scale) if isinstance(detector_scale, (tuple, list)) else (detector_scale, detector_scale)
         if len(ds) != 2 or not all(np.isfinite(float(v)) and float(v) > 0 for v in ds):
             raise nv.HrpError(f"PoseTracker: detector_scale {detector_scale!r}, want one or two positive numbers")
         if int(acquire_every) < 0 or (int(acquire_every) > 0 and detector is None):
             raise nv.HrpError(f"PoseTracker: acquire_every {acquire_every!r} (>= 0, and > 0 only with a detector)")
         self.detector, self.acquire_every, self._frame = detector, int(acquire_every), 0
+        thresholds = dict(min_support=min_support, min_coverage=min_coverage, min_iou=min_iou)
+        for name, v in thresholds.items():
+            if v is not None and not 0.0 <= float(v) <= 1.0:           # (false for NaN)
+                raise nv.HrpError(f"PoseTracker: {name} {v!r}, want a number in [0, 1] or None")
+        self.verifying = any(v is not None for v in thresholds.values())
+        if self.verifying and detector is None:
+            raise nv.HrpError("PoseTracker: min_support / min_coverage / min_iou need a detector")
+        if (min_iou is None) != (renderer is None):
+            raise nv.HrpError("PoseTracker: min_iou and renderer go together (the silhouette is rendered for the IoU only)")
+        if renderer is not None and np.asarray(K_original).size != 9:
+            raise nv.HrpError("PoseTracker: renderer with a per-stream K_original (the renderer has one camera)")
+        self.renderer, self._last = renderer, None
+        if self.verifying or bones is not None:
+            nkp = int(getattr(robot, "nkp", None) or len(robot.link_names))
+            if bones is None:
+                bones = [(i, i + 1) for i in range(nkp - 1)] if getattr(robot, "robot_type", None) in ("panda", "kuka") else []
+            bones = [tuple(int(i) for i in b) for b in bones]
+            if len(bones) > nv.TRACK_MAX_BONES or any(len(b) != 2 or not all(0 <= i < nkp for i in b) for b in bones):
+                raise nv.HrpError(f"PoseTracker: bones {bones!r}, want at most {nv.TRACK_MAX_BONES} pairs of key-point indices below {nkp}")
+            if not 1 <= int(verify_samples) <= nv.TRACK_MAX_SAMPLES:
+                raise nv.HrpError(f"PoseTracker: verify_samples {verify_samples!r}, want 1 .. {nv.TRACK_MAX_SAMPLES}")
+        self._verify = dict(thresholds, bones=bones or [], samples=int(verify_samples), min_fg=int(verify_min_fg),
+                            min_samples=int(verify_min_samples), min_prob=float(verify_min_prob), scale=(float(ds[0]), float(ds[1])))
         self._inv_scale = (C.c_double * 2)(1.0 / float(ds[0]), 1.0 / float(ds[1]))       # frame pixels per detector pixel
         device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if device.type != "cuda":
@@ -85,6 +118,8 @@ class PoseTracker:
         self.kp2d_original = new(B, self.nkp, 2, dt=torch.float32)
         self.jpeg_status = None
         self.seed_status = new(B, dt=torch.int32)
+        self.verify_status, self.verify_counts = new(B, dt=torch.int32), new(B, 4, dt=torch.int32)
+        self.verify_sums = new(B, 3, dt=torch.float64)
 
     def reset(self, kp2d=None, streams=None):
         """Seed the estimate: kp2d [B, nkp, 2] in original-image pixels (float64 is kept bit for bit), or None for no estimate.
@@ -101,6 +136,7 @@ class PoseTracker:
             raise nv.HrpError(f"PoseTracker.reset: kp2d {tuple(kp.shape)}, want {(idx.numel(), self.nkp, 2)}")
         self.kp2d.index_copy_(0, idx, kp)
         self.have.index_fill_(0, idx, 1)
+        self._last = None                    # the state is no longer the last prediction: no silhouette at the next verification
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
@@ -138,14 +174,67 @@ class PoseTracker:
                 self.have.data_ptr(), self.seed_status.data_ptr(), self._stream())
         return self.seed_status
 
+    def verify(self, mask, alpha=None):
+        """One launch (``hrp_track_verify``): every stream's estimate against the detector's foreground probability ``mask``
+        [B, 1, h, w] / [B, h, w] - the skeleton's support on the foreground (min_support), the foreground's coverage by the
+        estimate's box (min_coverage) and, with ``alpha`` [B, h, w] (the soft silhouette of the last prediction), their IoU
+        (min_iou).  A stream that fails an enabled criterion loses its estimate (``have`` = 0), so that a ``seed`` that follows takes
+        the detection.  Returns ``verify_status`` [B] int32 (_native.VERIFY_*), the tracker's own buffer; ``verify_counts`` [B, 4] =
+        (h_s, n_s, n_in, n_fg) and ``verify_sums`` [B, 3] float64 = (I, S, R) hold what was measured."""
+        def dev32(t, what):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise nv.HrpError(f"PoseTracker.verify: {what} must be a GPU tensor (there is no CPU path)")
+            if t.dim() not in (3, 4) or t.shape[0] != self.B or (t.dim() == 4 and t.shape[1] != 1):
+                raise nv.HrpError(f"PoseTracker.verify: {what} {tuple(t.shape)}, want [B, 1, h, w] or [B, h, w]")
+            return t.detach().float().contiguous()
+        mask = dev32(mask, "mask")
+        hm, wm = int(mask.shape[-2]), int(mask.shape[-1])
+        if alpha is not None:
+            alpha = dev32(alpha, "alpha")
+            if tuple(alpha.shape[-2:]) != (hm, wm):
+                raise nv.HrpError(f"PoseTracker.verify: alpha {tuple(alpha.shape)} and mask {tuple(mask.shape)} differ in size")
+        v, d = self._verify, nv.TrackVerifyDesc()
+        d.state_kp2d, d.state_have, d.mask = self.kp2d.data_ptr(), self.have.data_ptr(), mask.data_ptr()
+        d.alpha = None if alpha is None else alpha.data_ptr()
+        d.verify_status, d.counts, d.sums = self.verify_status.data_ptr(), self.verify_counts.data_ptr(), self.verify_sums.data_ptr()
+        d.B, d.nkp, d.hm, d.wm = self.B, self.nkp, hm, wm
+        d.nb, d.samples, d.min_fg, d.min_samples, d.min_prob = len(v["bones"]), v["samples"], v["min_fg"], v["min_samples"], v["min_prob"]
+        for i, (a, b) in enumerate(v["bones"]):
+            d.bones[i][0], d.bones[i][1] = a, b
+        d.scale[0], d.scale[1] = v["scale"]
+        d.extend_ratio[0], d.extend_ratio[1] = self._extend[0], self._extend[1]
+        off = lambda t: -1.0 if t is None else float(t)   # noqa: E731
+        d.min_support, d.min_coverage = off(v["min_support"]), off(v["min_coverage"])
+        d.min_iou = off(v["min_iou"]) if alpha is not None else -1.0
+        nv.call("hrp_track_verify", C.byref(d), self._stream())
+        return self.verify_status
+
+    def _silhouette(self, hm, wm):
+        """The soft silhouette [B, hm, wm] of the last prediction, or None when the state is not a prediction."""
+        if self.renderer is None or self._last is None:
+            return None
+        if tuple(self.renderer.image_size) != (hm, wm):
+            raise nv.HrpError(f"PoseTracker.acquire: the renderer draws {tuple(self.renderer.image_size)}, the detector's mask is {(hm, wm)}")
+        pose, rot, trans = self._last
+        if rot.dim() != 2 or rot.shape[1] != 6:
+            raise nv.HrpError(f"PoseTracker.acquire: rotations {tuple(rot.shape)}, the renderer takes the 6-D form")
+        with torch.no_grad():
+            return self.robot.get_rendered_masks(pose, rot, trans, self.renderer, root=self.reference_keypoint_id)
+
     def acquire(self, frames, force=False, min_inside=None, min_prob=0.5, min_peak=0.0):
         """Run the detector on the frames (uint8 [B, H, W, 3] on the device) and seed the streams without an estimate from it
-        (``seed``).  Returns ``seed_status``; never synchronises.  The NHWC -> NCHW view the detector takes is a torch copy."""
+        (``seed``).  With verification on (and not forced) ``verify`` runs in between, so a stream whose estimate disagrees with the
+        detector's mask takes this frame's detection in the same call.  Returns ``seed_status``; never synchronises.  The
+        NHWC -> NCHW view the detector takes is a torch copy."""
         if self.detector is None:
             raise nv.HrpError("PoseTracker.acquire: the tracker was built without a detector")
         self._check_frames(frames)
         with torch.no_grad():
             kp, mask, ms = self.detector(frames.permute(0, 3, 1, 2).contiguous())
+        if self.verifying and not force:
+            if not isinstance(mask, torch.Tensor) or mask.dim() not in (3, 4):
+                raise nv.HrpError("PoseTracker.acquire: verification needs the detector's foreground mask, and it returned none")
+            self.verify(mask, self._silhouette(int(mask.shape[-2]), int(mask.shape[-1])))
         return self.seed(kp, mask, ms, force=force, min_inside=min_inside, min_prob=min_prob, min_peak=min_peak)
 
     def prepare(self, frames):
@@ -190,7 +279,8 @@ class PoseTracker:
         Returns TrackResult(pose, rot, trans, kp3d, kp2d_original, depth, status, k_values), device tensors; kp2d_original,
         status and k_values are the tracker's own buffers.  With a detector and acquire_every = n > 0, every n-th frame (counted
         on the host, the first included) runs ``acquire`` first: only streams without an estimate take the detection, so a lost
-        stream recovers at the next scheduled detection without a read-back.  Without, exactly prepare - model - update."""
+        stream recovers at the next scheduled detection without a read-back; with verification on, a stream whose estimate disagrees
+        with the detector's mask does too.  Without, exactly prepare - model - update."""
         if isinstance(frames, (list, tuple)):
             frames = self.decode(frames)
         if self.acquire_every > 0:
@@ -201,5 +291,7 @@ class PoseTracker:
         with torch.no_grad():
             out = tuple(self.model(p["reg_images"], p["root_images"], p["k_values"], p["other_K"]))
         kp2d = self.update(out)
+        if self.renderer is not None:
+            self._last = (out[0], out[1], out[2])                # references: what the state now is the projection of
         return TrackResult(pose=out[0], rot=out[1], trans=out[2], kp3d=out[-1], kp2d_original=kp2d, depth=out[4] if len(out) > 4 else None, status=self.status,
                            k_values=self.k_values)

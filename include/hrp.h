@@ -73,6 +73,8 @@
  *                                                     lib/dataset/dream.py:171-216, 287-394; roboutils.py:59-156, 224-257;
  *                                                     lib/utils/geometries.py:360-395; lib/core/function.py:43-48, 88-98
  *   hrp_track_seed            tracker acquisition from a detector's key-points (CtRNet's KeyPointSegNet, hrp_kp_readout_fwd)
+ *   hrp_track_verify          the estimate against the detector's foreground map (skeleton support, box coverage, silhouette
+ *                             IoU); a stream that disagrees drops its estimate    scripts/train_sim2real.py (the IoU measure)
  *   hrp_track_update          the projection of the model's FK key-points into the original image, which becomes the estimate the
  *                             next frame is cropped from          lib/utils/geometries.py:100-115; lib/dataset/dream.py:171-216
  *   hrp_kp_readout_fwd        CtRNet's key-point branch: ConvTranspose2d read-out + spatial soft-argmax, the heat-map kept in fp32
@@ -1194,6 +1196,63 @@ enum { HRP_SEED_SKIPPED = 1, HRP_SEED_TAKEN = 2, HRP_SEED_REFUSED = 4 };
 int hrp_track_seed(const float* det_kp, int B, int nkp, const double* inv_scale, const float* mask, int hm, int wm, float min_prob,
                    const float* ms, float min_peak, int min_inside, int force, int W, int H, double* state_kp2d, int32_t* state_have,
                    int32_t* seed_status, void* stream);
+
+/* Tracker verification: the estimate of every stream is compared with the detector's foreground map of this frame, and a stream
+ * whose estimate does not agree loses it (have = 0), so that the hrp_track_seed launch that follows takes the detection
+ * (csrc/track_core.h track_verify, host and device code like track_seed; tests/track_verify_host_check.cpp, the float64 numpy
+ * statement is tests/track_verify_oracle.py).  hrp_track_verify is ONE launch, one 256-lane workgroup per stream.
+ *   state_kp2d [B, nkp, 2] float64 in frame pixels (read only), state_have [B] int32: the tracker's state;
+ *   scale: detector pixels per frame pixel (x, y), two host doubles that the caller computed itself (never 1 / inv_scale on the
+ *   device); mask [B, hm, wm] fp32 at detector resolution; alpha [B, hm, wm] fp32, the soft silhouette of the last prediction at
+ *   the same resolution, or NULL; bones [nb][2] key-point index pairs, by value; samples S per bone; extend_ratio as in
+ *   hrp_track_prepare; min_prob, min_fg, min_samples; min_support, min_coverage, min_iou: a negative value switches the criterion off;
+ *   verify_status [B] int32, counts [B, 4] int32 = (h_s, n_s, n_in, n_fg), sums [B, 3] float64 = (I, S, R): outputs.
+ * Per stream, in this order, float64 wherever a value is computed:
+ *   0. have == 0: HRP_VERIFY_SKIPPED; counts and sums are written as zero, the state is untouched.
+ *   1. a state coordinate, or its product with scale, is not finite: HRP_VERIFY_DROPPED, have = 0; counts and sums are zero.
+ *   2. d_i = u_i * scale: the key-points in detector pixels.
+ *   3. support: the sample points are every d_i and, for each bone (a, b) and j = 0 .. S - 1, d_a + t (d_b - d_a) with
+ *      t = (j + 0.5) / S.  A sample COUNTS (n_s) when 0 <= x < wm and 0 <= y < hm (tested in double before the cast); it HITS (h_s)
+ *      when mask[(int)y * wm + (int)x] >= min_prob (a NaN pixel compares false).  Samples outside the map are not counted at all.
+ *   4. coverage: the box is [min x - e0 w, min y - e1 h, max x + e0 w, max y + e1 h] over all d_i, w = max x - min x,
+ *      h = max y - min y, e = extend_ratio.  A pixel is foreground (n_fg) when mask >= min_prob; it is inside (n_in) when it is
+ *      foreground and its centre (x + 0.5, y + 0.5) lies in the closed box.
+ *   5. IoU, only with alpha: I = sum m a, S = sum m, R = sum a over the whole map, every fp32 value widened to double, products in
+ *      double, sums in a fixed order; iou = I / (S + R - I) (s2r_sums_kernel's measure).  Without alpha I = R = 0 and S = sum m.
+ *   6. n_fg < min_fg: HRP_VERIFY_UNDECIDED (the detector sees no robot), the state is untouched.  Otherwise every enabled criterion
+ *      can fail, each comparison written !(score >= min) so that a NaN score fails: support on !(h_s / n_s >= min_support), not
+ *      applied when n_s < min_samples; coverage on !(n_in / n_fg >= min_coverage); IoU on !(iou >= min_iou).  Any failure: have = 0
+ *      and HRP_VERIFY_DROPPED | HRP_VERIFY_FAIL_*, one bit per failed criterion.  None: HRP_VERIFY_KEPT.
+ * The key-point coordinates of the state are never written, only have.  Every value is range-checked before every float -> int
+ * conversion and every mask index is tested against hm, wm immediately before its load.  The sums of one stream are taken in an
+ * order that depends only on the arguments (and on the 16-byte alignment of the stream's maps): no atomics, two runs are
+ * bit-equal.  The grid depends on B only, caller-owned buffers, no host synchronisation: graph-capturable.
+ * Refused (HRP_ERR_ARG, nothing is launched): null required pointers, B outside 1 .. 65535, nkp outside 1 .. HRP_TRACK_MAX_KP,
+ * hm / wm outside 1 .. HRP_TRACK_MAX_SIZE, nb outside 0 .. HRP_TRACK_MAX_BONES, a bone index outside [0, nkp), samples outside
+ * 1 .. 64, scale or extend_ratio not finite, scale not positive, a threshold above 1 or NaN, min_iou >= 0 without alpha. */
+enum {
+  HRP_VERIFY_SKIPPED = 1, HRP_VERIFY_KEPT = 2, HRP_VERIFY_UNDECIDED = 4, HRP_VERIFY_DROPPED = 8,
+  HRP_VERIFY_FAIL_SUPPORT = 16, HRP_VERIFY_FAIL_COVERAGE = 32, HRP_VERIFY_FAIL_IOU = 64
+};
+#define HRP_TRACK_MAX_BONES 32
+#define HRP_TRACK_MAX_SAMPLES 64
+typedef struct {
+  const double* state_kp2d;
+  int32_t* state_have;
+  const float* mask;
+  const float* alpha;                                /* or NULL */
+  int32_t* verify_status;
+  int32_t* counts;
+  double* sums;
+  int32_t B, nkp, hm, wm;
+  int32_t nb, samples, min_fg, min_samples;
+  int32_t bones[HRP_TRACK_MAX_BONES][2];
+  double scale[2], extend_ratio[2];
+  double min_support, min_coverage, min_iou;
+  float min_prob;
+  int32_t reserved;
+} hrp_track_verify_desc;
+int hrp_track_verify(const hrp_track_verify_desc* d, void* stream);
 
 /* CtRNet key-point read-out and spatial soft-argmax, forward only (csrc/kp_readout.hip; reference
  * lib/models/ctrnet/keypoint_seg_resnet.py:29-33 KeypointUpSample.forward, 75-100 SpatialSoftArgmax.forward, 137-143):

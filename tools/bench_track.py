@@ -10,8 +10,13 @@
 (d) acquisition at B = 1, 4: ``PoseTracker.acquire`` (CtRNet's ``seg_mask_inference.detect`` in bf16 on the full frame + the seed
     launch), the key-point read-out launch pair alone on the detector's 30 x 40 x 2048 feature, and ``step`` with
     ``acquire_every=30``.  Nothing is gated on speed.
+(e) ``--verify``: verification at B = 1, 4 next to the figures of (d): ``acquire`` (not forced; every stream has an estimate, so the
+    seed launch skips them all) without verification, with the skeleton criteria, and with a box mesh of 432 faces as renderer
+    (mesh pose + rasteriser + the IoU); the ``hrp_track_verify`` launch alone by device events on the detector's 240 x 320 map and
+    on a 480 x 640 one, without and with a silhouette.  The thresholds are 0, so every measurement is taken and no stream is
+    dropped from one repetition to the next.
 Also: whether the model's forward synchronises (torch's sync debug mode around one call).  Prints one JSON line per B and row.
-Run on the GPU box: ``python tools/bench_track.py`` (``--acquire``: the rows of (d) only)."""
+Run on the GPU box: ``python tools/bench_track.py`` (``--acquire``: the rows of (d) only; ``--verify``: the rows of (d) and (e) only)."""
 import json
 import os
 import statistics
@@ -196,13 +201,51 @@ def bench_acquire(model, robot, B, seq):
                 seed_status=trk.seed_status.cpu().tolist())
 
 
+def bench_verify(model, robot, B, seq):
+    """(e): acquire with verification, and the verify launch alone."""
+    from hrpe_amd.lib.models.ctrnet.mask_inference import seg_mask_inference
+    from bench_sim2real import grid_box_mesh
+    torch.manual_seed(1)
+    det = seg_mask_inference((615.0, 615.0, 320.0, 240.0), "azure", image_hw=(H, W), allow_random_init=True).to(DEV)
+    det.set_compute_dtype(torch.bfloat16)
+    scale = det.args.scale
+    mesh = tuple(t.to(DEV) for t in grid_box_mesh(2))
+    renderer = robot.set_robot_renderer(torch.tensor(K), (H, W), scale=scale, device=DEV, mesh=mesh)
+    common = dict(streams=B, device=DEV, detector=det.detect, detector_scale=scale)
+    rows = dict(B=B, row="verify", mesh_faces=int(mesh[2].shape[0]))
+    trackers = {}
+    for name, kw in (("plain", {}), ("skeleton", dict(min_support=0.0, min_coverage=0.0)),
+                     ("silhouette", dict(min_support=0.0, min_coverage=0.0, min_iou=0.0, renderer=renderer))):
+        trk = trackers[name] = PoseTracker(model, robot, K, (H, W), **common, **kw)
+        trk.reset(seeds(B))
+        if name == "silhouette":         # a pose in front of the camera stands in for the last prediction
+            trk._last = (torch.zeros(B, robot.dof, device=DEV), torch.tensor([1.0, 0, 0, 0, 1, 0], device=DEV).repeat(B, 1),
+                         torch.tensor([0.0, 0.0, 1.5], device=DEV).repeat(B, 1))
+        lat, thr = wall(trk.acquire, seq, warmup=6, n=30)
+        rows[f"acquire_{name}_latency_ms"], rows[f"acquire_{name}_pipelined_ms"] = round(lat, 3), round(thr, 3)
+        rows[f"{name}_status"] = trk.verify_status.cpu().tolist()
+    trk = trackers["silhouette"]
+    for hm, wm in ((H // 2, W // 2), (H, W)):
+        yy, xx = torch.meshgrid(torch.arange(hm, device=DEV), torch.arange(wm, device=DEV), indexing="ij")
+        blob = ((((xx - wm / 2) / (wm / 4)) ** 2 + ((yy - hm / 2) / (hm / 4)) ** 2) <= 1).float()
+        mask = (blob * 0.9).repeat(B, 1, 1).contiguous()
+        alpha = torch.roll(mask, (hm // 8, wm // 8), (1, 2)).contiguous()
+        trk._verify["scale"] = (wm / W, hm / H)
+        rows[f"verify_{hm}x{wm}_us"] = round(median_us(lambda: trk.verify(mask), warmup=20, reps=200), 1)
+        rows[f"verify_{hm}x{wm}_silhouette_us"] = round(median_us(lambda: trk.verify(mask, alpha), warmup=20, reps=200), 1)
+        rows[f"verify_{hm}x{wm}_counts"] = trk.verify_counts.cpu().tolist()
+    return rows
+
+
 def main():
     model = model_bf16()
     robot = URDFRobot("panda")
     for B in (1, 4):
         seq = [torch.from_numpy(np.stack([dream_scene.texture(H, W, 10 * t + b) for b in range(B)])).to(DEV) for t in range(4)]
         print(json.dumps(bench_acquire(model, robot, B, seq)), flush=True)
-    if "--acquire" in sys.argv[1:]:
+        if "--verify" in sys.argv[1:]:
+            print(json.dumps(bench_verify(model, robot, B, seq)), flush=True)
+    if "--acquire" in sys.argv[1:] or "--verify" in sys.argv[1:]:
         return
     for B in (1, 4, 16):
         seq = [torch.from_numpy(np.stack([dream_scene.texture(H, W, 10 * t + b) for b in range(B)])).to(DEV) for t in range(4)]
