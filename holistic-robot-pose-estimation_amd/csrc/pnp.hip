@@ -3,7 +3,10 @@
 // fp64 inside.  Every cross-lane sum is a fixed-order butterfly whose lane-0 result is broadcast, so the values every lane
 // branches on are identical and two identical calls return identical bytes.  Small dense systems live either in registers
 // (compile-time indices only) or in LDS (the Jacobi eigen-solves, whose pivots are data dependent).
+// The robust forward (pnp_robust_kernel) puts a consensus over P3P hypotheses in front of the same LM: lane = hypothesis while it
+// hypothesises and scores (pnp_minimal.h), lane = point again for the refits.
 #include "hrp_common.h"
+#include "pnp_minimal.h"
 
 namespace hrp {
 namespace {
@@ -370,7 +373,7 @@ __device__ __forceinline__ void quat_to_R(const double (&q)[4], double (&R)[3][3
 __device__ __forceinline__ double sq3(double a, double b, double c) { return a * a + b * b + c * c; }
 
 // EPnP (Lepetit, Moreno-Noguer, Fua 2009) as OpenCV's SOLVEPNP_EPNP: returns the best of the N = 1, 2, 3 beta solutions
-__device__ Pose epnp(const double (&K)[9], const double (&X)[3], const double (&x)[2], bool on, int n, int lane, double* sA, double* sV,
+__device__ __forceinline__ Pose epnp(const double (&K)[9], const double (&X)[3], const double (&x)[2], bool on, int n, int lane, double* sA, double* sV,
                      double* sN, double* sL, double* sRho) {
   const double m = on ? 1.0 : 0.0, inv_n = 1.0 / n;
   // control points: centroid + principal axes scaled by sqrt(eigenvalue / n)
@@ -573,37 +576,15 @@ __device__ Pose epnp(const double (&K)[9], const double (&X)[3], const double (&
   return best;
 }
 
-__global__ __launch_bounds__(64) void pnp_solve_kernel(const float* __restrict__ pts2d, const float* __restrict__ pts3d, int z_stride,
-                                                       const float* __restrict__ Km, int K_stride, const float* __restrict__ ini_pose,
-                                                       int n, float* __restrict__ P6d, int* __restrict__ status, float* __restrict__ rms) {
-  __shared__ double sA[144], sV[144], sN[48], sL[60], sRho[6];
-  const int b = blockIdx.x, lane = threadIdx.x;
-  const bool on = lane < n;
-  const int li = on ? lane : 0;
-  double K[9], X[3], x[2];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) K[k] = Km[(size_t)b * K_stride + k];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) X[k] = pts3d[(size_t)b * z_stride + li * 3 + k];
-  x[0] = pts2d[((size_t)b * n + li) * 2];
-  x[1] = pts2d[((size_t)b * n + li) * 2 + 1];
-
-  Pose y;
-  if (ini_pose) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      y.w[k] = ini_pose[b * 6 + k];
-      y.t[k] = ini_pose[b * 6 + 3 + k];
-    }
-  } else {
-    y = epnp(K, X, x, on, n, lane, sA, sV, sN, sL, sRho);
-  }
-
-  // Levenberg-Marquardt on (w, t): the objective of SOLVEPNP_ITERATIVE, Marquardt's diagonal damping
-  double cost, JtJ[6][6], Jte[6];
+// Levenberg-Marquardt on (w, t) over the lanes with `on` set: the objective of SOLVEPNP_ITERATIVE, Marquardt's diagonal damping.
+// y is refined in place; cost = the sum of squares at y, it = trials, converged = 1 unless the trial cap ended the loop.
+__device__ __forceinline__ void lm_refine(Pose& y, const double (&K)[9], const double (&X)[3], const double (&x)[2], bool on, double& cost,
+                         int& it, int& converged) {
+  double JtJ[6][6], Jte[6];
   lm_eval(y, K, X, x, on, cost, JtJ, Jte);
   double lambda = 1e-3;
-  int it = 0, converged = 0;
+  it = 0;
+  converged = 0;
   for (; it < PNP_LM_MAX_IT; ++it) {
     double A[6][6], st[6];
 #pragma unroll
@@ -643,7 +624,10 @@ __global__ __launch_bounds__(64) void pnp_solve_kernel(const float* __restrict__
     // no step of any length lowers the cost at this precision: the minimum is reached
     if (lambda > 1e10) { converged = 1; ++it; break; }
   }
-  // rotation normalised to |w| <= pi
+}
+
+// rotation normalised to |w| <= pi
+__device__ __forceinline__ void normalise_rotation(Pose& y) {
   double th = sqrt(sq3(y.w[0], y.w[1], y.w[2]));
   if (th > M_PI) {
     double tn = fmod(th, 2.0 * M_PI);
@@ -652,6 +636,38 @@ __global__ __launch_bounds__(64) void pnp_solve_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < 3; ++k) y.w[k] *= f;
   }
+}
+
+__global__ __launch_bounds__(64) void pnp_solve_kernel(const float* __restrict__ pts2d, const float* __restrict__ pts3d, int z_stride,
+                                                       const float* __restrict__ Km, int K_stride, const float* __restrict__ ini_pose,
+                                                       int n, float* __restrict__ P6d, int* __restrict__ status, float* __restrict__ rms) {
+  __shared__ double sA[144], sV[144], sN[48], sL[60], sRho[6];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const bool on = lane < n;
+  const int li = on ? lane : 0;
+  double K[9], X[3], x[2];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = Km[(size_t)b * K_stride + k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) X[k] = pts3d[(size_t)b * z_stride + li * 3 + k];
+  x[0] = pts2d[((size_t)b * n + li) * 2];
+  x[1] = pts2d[((size_t)b * n + li) * 2 + 1];
+
+  Pose y;
+  if (ini_pose) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      y.w[k] = ini_pose[b * 6 + k];
+      y.t[k] = ini_pose[b * 6 + 3 + k];
+    }
+  } else {
+    y = epnp(K, X, x, on, n, lane, sA, sV, sN, sL, sRho);
+  }
+
+  double cost;
+  int it, converged;
+  lm_refine(y, K, X, x, on, cost, it, converged);
+  normalise_rotation(y);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -666,19 +682,205 @@ __global__ __launch_bounds__(64) void pnp_solve_kernel(const float* __restrict__
   }
 }
 
+// ---- robust forward: consensus over P3P hypotheses, then LM on the consensus set (pnp_minimal.h holds the per-hypothesis core) -------
+// The reference's BPnP_fast starts from cv2.solvePnPRansac (BPnP.py:267); here the minimal sets are enumerated, not drawn, and each is
+// solved by P3P.  Lane = hypothesis in passes of 64 (each lane solves its triple and scores every root against the sample's usable
+// points, which lie in LDS), a butterfly picks the winner by (count, -ssq, lower hypothesis), then lane = point again: LM on the
+// winner's inliers, re-score, refit while the set changes (three refits at most), and with refine_all one more LM over all usable points.
+// Below min_inliers the sample takes pnp_solve_kernel's path (EPnP + LM) over its usable points.
+__device__ __forceinline__ bool lane_inlier(const Pose& y, const double (&K)[9], const double (&X)[3], const double (&x)[2], double thr2) {
+  double R[3][3], e2;
+  pnpmin::aa_to_rot(y.w, R);
+  return pnpmin::reproj_e2(R, y.t, K, X, x, e2) && e2 < thr2;
+}
+
+__global__ __launch_bounds__(64) void pnp_robust_kernel(const float* __restrict__ pts2d, const float* __restrict__ pts3d, int z_stride,
+                                                        const float* __restrict__ Km, int K_stride, const unsigned char* __restrict__ valid,
+                                                        int n, double thr, int min_inliers, int max_hypotheses, unsigned seed, int refine_all,
+                                                        float* __restrict__ P6d, unsigned char* __restrict__ inliers,
+                                                        int* __restrict__ status, float* __restrict__ rms) {
+  __shared__ double sA[144], sV[144], sN[48], sL[60], sRho[6];
+  __shared__ double sX[64][3], sx[64][2], sF[64][3];
+  __shared__ int sIdx[64];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const double thr2 = thr * thr;
+  double K[9], X[3], x[2], F[3] = {0.0, 0.0, 1.0};
+#pragma unroll
+  for (int k = 0; k < 9; ++k) K[k] = Km[(size_t)b * K_stride + k];
+  bool ok = lane < n;
+  {
+    const int li = ok ? lane : 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) X[k] = pts3d[(size_t)b * z_stride + li * 3 + k];
+    x[0] = pts2d[((size_t)b * n + li) * 2];
+    x[1] = pts2d[((size_t)b * n + li) * 2 + 1];
+    ok = ok && pnpmin::point_valid(valid ? valid + (size_t)b * n + li : nullptr, X, x) && pnpmin::bearing(K, x, F);
+  }
+  // the usable points, compacted in lane order; a lane without one holds a copy of the first (as pnp_solve_kernel's idle lanes hold
+  // point 0), so that nothing non-finite enters the sums it is masked out of
+  const unsigned long long vmask = __ballot(ok);
+  const int m = __popcll(vmask);
+  const int first = m ? __ffsll((long long)vmask) - 1 : 0;
+  if (ok) sIdx[__popcll(vmask & ((1ull << lane) - 1ull))] = lane;
+  if (!ok) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) X[k] = pts3d[(size_t)b * z_stride + first * 3 + k];
+    x[0] = pts2d[((size_t)b * n + first) * 2];
+    x[1] = pts2d[((size_t)b * n + first) * 2 + 1];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    sX[lane][k] = X[k];
+    sF[lane][k] = F[k];
+  }
+  sx[lane][0] = x[0];
+  sx[lane][1] = x[1];
+  __syncthreads();
+
+  // hypothesise and score
+  const int H = pnpmin::hypothesis_count(m, max_hypotheses);
+  int best_count = -1, best_h = 0x7fffffff;
+  double best_ssq = 0.0, bR[3][3], bt[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    bt[r] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) bR[r][k] = r == k ? 1.0 : 0.0;
+  }
+  for (int h = lane; h < H; h += 64) {
+    int tri[3];
+    pnpmin::hypothesis_triple(h, m, max_hypotheses, seed, tri[0], tri[1], tri[2]);
+    double X3[3][3], f3[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int p = sIdx[tri[a]];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        X3[a][k] = sX[p][k];
+        f3[a][k] = sF[p][k];
+      }
+    }
+    pnpmin::P3P S;
+    pnpmin::p3p_prepare(X3, f3, S);
+#pragma nounroll
+    for (int slot = 0; slot < 4; ++slot) {
+      double R[3][3], t[3];
+      if (!pnpmin::p3p_pose(S, slot, R, t)) continue;
+      int count = 0;
+      double ssq = 0.0;
+      for (int q = 0; q < m; ++q) {
+        const int p = sIdx[q];
+        const double Xp[3] = {sX[p][0], sX[p][1], sX[p][2]}, xp[2] = {sx[p][0], sx[p][1]};
+        double e2;
+        if (pnpmin::reproj_e2(R, t, K, Xp, xp, e2) && e2 < thr2) {
+          ++count;
+          ssq += e2;
+        }
+      }
+      if (pnpmin::score_better(count, ssq, best_count, best_ssq)) {
+        best_count = count;
+        best_ssq = ssq;
+        best_h = h;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          bt[r] = t[r];
+#pragma unroll
+          for (int k = 0; k < 3; ++k) bR[r][k] = R[r][k];
+        }
+      }
+    }
+  }
+  // the winner: more inliers, then the smaller sum of squares, then the lower hypothesis (a lane's own ties went to the lower
+  // hypothesis and root already); the order is total, so every lane ends with the same triple
+  {
+    int wc = best_count, wh = best_h;
+    double ws = best_ssq;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int oc = __shfl_xor(wc, o, 64), oh = __shfl_xor(wh, o, 64);
+      const double os = __shfl_xor(ws, o, 64);
+      if (pnpmin::score_better(oc, os, wc, ws) || (oc == wc && os == ws && oh < wh)) {
+        wc = oc;
+        ws = os;
+        wh = oh;
+      }
+    }
+    const int src = wh & 63;
+    best_count = wc;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      bt[r] = __shfl(bt[r], src, 64);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) bR[r][k] = __shfl(bR[r][k], src, 64);
+    }
+  }
+  const bool consensus = best_count >= min_inliers;      // the same in every lane
+
+  Pose y;
+  bool fit;
+  if (consensus) {
+    pnpmin::rot_to_aa(bR, y.w);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) y.t[k] = bt[k];
+    double e2;
+    fit = ok && pnpmin::reproj_e2(bR, bt, K, X, x, e2) && e2 < thr2;
+  } else {
+    y = epnp(K, X, x, ok, m, lane, sA, sV, sN, sL, sRho);
+    fit = ok;
+  }
+  double cost = 0.0;
+  int its = 0, converged = 0, nfit = 0;
+  bool over_all = false;
+  for (int round = 0;; ++round) {
+    int it;
+    lm_refine(y, K, X, x, fit, cost, it, converged);
+    its += it;
+    const unsigned long long fmask = __ballot(fit);
+    nfit = __popcll(fmask);
+    if (!consensus || over_all) break;
+    const bool in = ok && lane_inlier(y, K, X, x, thr2);
+    if (__ballot(in) != fmask && round < 2) {
+      fit = in;
+      continue;
+    }
+    if (!refine_all) break;
+    fit = ok;
+    over_all = true;
+  }
+  normalise_rotation(y);
+  const bool in = ok && lane_inlier(y, K, X, x, thr2);
+  const int count = __popcll(__ballot(in));
+  if (lane < n) inliers[(size_t)b * n + lane] = in ? 1 : 0;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      P6d[b * 6 + k] = (float)y.w[k];
+      P6d[b * 6 + 3 + k] = (float)y.t[k];
+    }
+    status[b * 4] = (consensus ? 0 : HRP_PNP_NO_CONSENSUS) | (converged ? HRP_PNP_CONVERGED : 0) | (m < 4 ? HRP_PNP_FEW_POINTS : 0);
+    status[b * 4 + 1] = its;
+    status[b * 4 + 2] = count;
+    status[b * 4 + 3] = H;
+    rms[b] = nfit ? (float)sqrt(cost / nfit) : 0.0f;
+  }
+}
+
 // ---- backward: the reference's implicit-function gradient (BPnP.py:50-111, 154-236, fast variant :280-341) ----------------------
 // f_j = sum_i coef_ij . r_i,  r_i = x_i S_i - (K [R|t] [z_i; 1])_{0:2},  coef_ij = -2 d pi_i / d y_j;  the rows of J_fy (6 x 6) and
 // J_fK (6 x 9) are reduced over the points, J_fx (6 x 2) and J_fz (6 x 3) stay per lane.  `fast` drops the coef derivatives.
+// mask (optional, [B, n] bytes): a point whose byte is 0 adds nothing to the reduced rows and gets zero grad_x / grad_z.
 __global__ __launch_bounds__(64) void pnp_bwd_kernel(const float* __restrict__ pts2d, const float* __restrict__ pts3d, int z_stride,
                                                      const float* __restrict__ Km, int K_stride, const float* __restrict__ P6d,
                                                      const float* __restrict__ gout, int n, int fast, float* __restrict__ grad_x,
-                                                     float* __restrict__ grad_z, float* __restrict__ grad_K, int* __restrict__ status) {
+                                                     float* __restrict__ grad_z, float* __restrict__ grad_K, int* __restrict__ status,
+                                                     const unsigned char* __restrict__ mask) {
   __shared__ double sR[3][3][10];  // the rotation jet: value, gradient (3), Hessian (6)
   __shared__ double sJy[6][6], sJK[6][9];
   const int b = blockIdx.x, lane = threadIdx.x;
   const bool on = lane < n;
   const int li = on ? lane : 0;
-  const double m = on ? 1.0 : 0.0;
+  const bool use = on && (!mask || mask[(size_t)b * n + li]);
+  const double m = use ? 1.0 : 0.0;
   double K[9], X[3], x[2], t[3];
 #pragma unroll
   for (int k = 0; k < 9; ++k) K[k] = Km[(size_t)b * K_stride + k];
@@ -686,6 +888,10 @@ __global__ __launch_bounds__(64) void pnp_bwd_kernel(const float* __restrict__ p
   for (int k = 0; k < 3; ++k) X[k] = pts3d[(size_t)b * z_stride + li * 3 + k];
   x[0] = pts2d[((size_t)b * n + li) * 2];
   x[1] = pts2d[((size_t)b * n + li) * 2 + 1];
+  if (mask && !use) {      // whatever a masked-out point holds (NaN included) stays out of the sums it is multiplied out of
+    X[0] = X[1] = X[2] = 0.0;
+    x[0] = x[1] = 0.0;
+  }
   {
     double w[3];
 #pragma unroll
@@ -864,14 +1070,14 @@ __global__ __launch_bounds__(64) void pnp_bwd_kernel(const float* __restrict__ p
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j < 6; ++j) s -= v[j] * Jx[j][k];
-      grad_x[((size_t)b * n + lane) * 2 + k] = (float)s;
+      grad_x[((size_t)b * n + lane) * 2 + k] = use ? (float)s : 0.0f;
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       double s = 0.0;
 #pragma unroll
       for (int j = 0; j < 6; ++j) s -= v[j] * Jz[j][k];
-      grad_z[((size_t)b * n + lane) * 3 + k] = (float)s;
+      grad_z[((size_t)b * n + lane) * 3 + k] = use ? (float)s : 0.0f;
     }
   }
   if (lane < 9) {
@@ -908,17 +1114,49 @@ extern "C" int hrp_pnp_solve(const float* pts2d, const float* pts3d, int pts3d_s
   return check_launch("pnp_solve");
 }
 
+namespace {
+int pnp_bwd_launch(const char* what, const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
+                   const float* grad_out, int B, int n, int fast, float* grad_x, float* grad_z, float* grad_K, float* grad_z_sum,
+                   float* grad_K_sum, int* status, const unsigned char* mask, void* stream) {
+  HRP_REQUIRE(pts2d && pts3d && K && P6d && grad_out && grad_x && grad_z && grad_K && B > 0, "%s: bad args", what);
+  HRP_REQUIRE(n >= 4 && n <= 64, "%s: %d points (4..64 supported)", what, n);
+  HRP_REQUIRE(pts3d_stride == 0 || pts3d_stride == 3 * n, "%s: pts3d stride %d (0 or 3n)", what, pts3d_stride);
+  HRP_REQUIRE(K_stride == 0 || K_stride == 9, "%s: K stride %d (0 or 9)", what, K_stride);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pnp_bwd_kernel, dim3(B), dim3(64), 0, s, pts2d, pts3d, pts3d_stride, K, K_stride, P6d, grad_out, n, fast, grad_x,
+                     grad_z, grad_K, status, mask);
+  if (grad_z_sum) hipLaunchKernelGGL(pnp_batch_sum_kernel, dim3(cdiv(3 * n, 64)), dim3(64), 0, s, grad_z, B, 3 * n, grad_z_sum);
+  if (grad_K_sum) hipLaunchKernelGGL(pnp_batch_sum_kernel, dim3(1), dim3(64), 0, s, grad_K, B, 9, grad_K_sum);
+  return check_launch(what);
+}
+}  // namespace
+
 extern "C" int hrp_pnp_bwd(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
                            const float* grad_out, int B, int n, int fast, float* grad_x, float* grad_z, float* grad_K, float* grad_z_sum,
                            float* grad_K_sum, int* status, void* stream) {
-  HRP_REQUIRE(pts2d && pts3d && K && P6d && grad_out && grad_x && grad_z && grad_K && B > 0, "pnp_bwd: bad args");
-  HRP_REQUIRE(n >= 4 && n <= 64, "pnp_bwd: %d points (4..64 supported)", n);
-  HRP_REQUIRE(pts3d_stride == 0 || pts3d_stride == 3 * n, "pnp_bwd: pts3d stride %d (0 or 3n)", pts3d_stride);
-  HRP_REQUIRE(K_stride == 0 || K_stride == 9, "pnp_bwd: K stride %d (0 or 9)", K_stride);
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(pnp_bwd_kernel, dim3(B), dim3(64), 0, s, pts2d, pts3d, pts3d_stride, K, K_stride, P6d, grad_out, n, fast, grad_x,
-                     grad_z, grad_K, status);
-  if (grad_z_sum) hipLaunchKernelGGL(pnp_batch_sum_kernel, dim3(cdiv(3 * n, 64)), dim3(64), 0, s, grad_z, B, 3 * n, grad_z_sum);
-  if (grad_K_sum) hipLaunchKernelGGL(pnp_batch_sum_kernel, dim3(1), dim3(64), 0, s, grad_K, B, 9, grad_K_sum);
-  return check_launch("pnp_bwd");
+  return pnp_bwd_launch("pnp_bwd", pts2d, pts3d, pts3d_stride, K, K_stride, P6d, grad_out, B, n, fast, grad_x, grad_z, grad_K, grad_z_sum,
+                        grad_K_sum, status, nullptr, stream);
+}
+
+extern "C" int hrp_pnp_bwd_masked(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
+                                  const float* grad_out, const unsigned char* mask, int B, int n, int fast, float* grad_x, float* grad_z,
+                                  float* grad_K, float* grad_z_sum, float* grad_K_sum, int* status, void* stream) {
+  HRP_REQUIRE(mask, "pnp_bwd_masked: bad args");
+  return pnp_bwd_launch("pnp_bwd_masked", pts2d, pts3d, pts3d_stride, K, K_stride, P6d, grad_out, B, n, fast, grad_x, grad_z, grad_K,
+                        grad_z_sum, grad_K_sum, status, mask, stream);
+}
+
+extern "C" int hrp_pnp_solve_robust(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride,
+                                    const unsigned char* valid, int B, int n, double reproj_error, int min_inliers, int max_hypotheses,
+                                    unsigned seed, int refine_all, float* P6d, unsigned char* inliers, int* status, float* rms, void* stream) {
+  HRP_REQUIRE(pts2d && pts3d && K && P6d && inliers && status && rms && B > 0, "pnp_solve_robust: bad args");
+  HRP_REQUIRE(n >= 4 && n <= 64, "pnp_solve_robust: %d points (4..64 supported)", n);
+  HRP_REQUIRE(pts3d_stride == 0 || pts3d_stride == 3 * n, "pnp_solve_robust: pts3d stride %d (0 or 3n)", pts3d_stride);
+  HRP_REQUIRE(K_stride == 0 || K_stride == 9, "pnp_solve_robust: K stride %d (0 or 9)", K_stride);
+  HRP_REQUIRE(reproj_error > 0.0 && reproj_error <= 1e150, "pnp_solve_robust: reprojection threshold %g px (positive, finite)", reproj_error);
+  HRP_REQUIRE(min_inliers >= 4 && min_inliers <= 64, "pnp_solve_robust: min_inliers %d (4..64)", min_inliers);
+  HRP_REQUIRE(max_hypotheses >= 1 && max_hypotheses <= (1 << 20), "pnp_solve_robust: max_hypotheses %d (1..2^20)", max_hypotheses);
+  hipLaunchKernelGGL(pnp_robust_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, pts2d, pts3d, pts3d_stride, K, K_stride, valid, n,
+                     reproj_error, min_inliers, max_hypotheses, seed, refine_all, P6d, inliers, status, rms);
+  return check_launch("pnp_solve_robust");
 }

@@ -4,7 +4,8 @@ wrapper (the reference's checkpoints carry the ``module.`` prefix), the detectio
 * ``inference_batch_images_onlyseg`` (102-111), the mask network's call, unchanged;
 * ``inference_batch_images_seg_kp`` (91-100): key-points and foreground probability from one plan;
 * ``inference_batch_images`` / ``inference_single_image`` (49-89): the same, plus ``cTr`` from the GPU PnP solver (``BPnP_m3d`` /
-  ``BPnP``, lib/utils/BPnP.py, csrc/pnp.hip - the reference calls OpenCV on the host);
+  ``BPnP``, lib/utils/BPnP.py, csrc/pnp.hip - the reference calls OpenCV on the host), or, with ``reproj_error`` given, from the
+  robust solver (``BPnP_robust``: consensus over P3P hypotheses, LM on the inliers), the inlier mask kept as ``last_inliers``;
 * ``cTr_to_pose_matrix`` (114-124), ``to_valid_R_batch`` (126-129).
 
 Not built: ``render_single_robot_mask`` and ``train_on_batch`` (131-194; training the key-point network is out of scope)."""
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 from hrpe_amd import _native as nv
-from hrpe_amd.lib.utils.BPnP import BPnP, BPnP_m3d
+from hrpe_amd.lib.utils.BPnP import BPnP, BPnP_m3d, BPnP_robust
 from hrpe_amd.lib.utils.geometries import angle_axis_to_rotation_matrix
 from .keypoint_seg_resnet import KeyPointSegNet
 
@@ -82,20 +83,31 @@ class CtRNet(torch.nn.Module):
         points_2d, segmentation = self._seg_kp(img)
         return points_2d, torch.sigmoid(segmentation)
 
-    def inference_batch_images(self, img, joint_angles, points_3d=None):
+    def _robust_pose(self, points_2d, pts, reproj_error):
+        cTr, self.last_inliers = BPnP_robust.apply(points_2d, pts.to(points_2d.device), self.K, float(reproj_error))
+        return cTr
+
+    def inference_batch_images(self, img, joint_angles, points_3d=None, reproj_error=None):
         """img [B, 3, H, W], joint_angles [B, dof] -> (cTr [B, 6] angle-axis + translation from BPnP_m3d, points_2d [B, k, 2],
-        foreground probability) (CtRNet.py:68-89).  points_3d [B, k, 3]: see ``_points_3d``."""
+        foreground probability) (CtRNet.py:68-89).  points_3d [B, k, 3]: see ``_points_3d``.  reproj_error (px): cTr from
+        ``BPnP_robust`` instead, a key-point farther than that from the consensus pose has no say; ``self.last_inliers`` [B, k] bool."""
         points_2d, segmentation = self._seg_kp(img)
         pts = self._points_3d(joint_angles, points_3d, True)
-        cTr = BPnP_m3d.apply(points_2d, pts.to(points_2d.device), self.K)
+        if reproj_error is not None:
+            cTr = self._robust_pose(points_2d, pts, reproj_error)
+        else:
+            cTr = BPnP_m3d.apply(points_2d, pts.to(points_2d.device), self.K)
         return cTr, points_2d, torch.sigmoid(segmentation)
 
-    def inference_single_image(self, img, joint_angles, points_3d=None):
+    def inference_single_image(self, img, joint_angles, points_3d=None, reproj_error=None):
         """img [3, H, W], joint_angles [dof] -> (cTr [1, 6] from BPnP, points_2d [1, k, 2], foreground probability [1, 1, H, W])
-        (CtRNet.py:49-66).  points_3d [k, 3]: see ``_points_3d``."""
+        (CtRNet.py:49-66).  points_3d [k, 3]: see ``_points_3d``.  reproj_error: as ``inference_batch_images``."""
         points_2d, segmentation = self._seg_kp(img[None])
         pts = self._points_3d(joint_angles, points_3d, False)
-        cTr = BPnP.apply(points_2d, pts.to(points_2d.device), self.K)
+        if reproj_error is not None:
+            cTr = self._robust_pose(points_2d, pts, reproj_error)
+        else:
+            cTr = BPnP.apply(points_2d, pts.to(points_2d.device), self.K)
         return cTr, points_2d, torch.sigmoid(segmentation)
 
     def cTr_to_pose_matrix(self, cTr):

@@ -5,8 +5,14 @@ and return P_6d [B,6] (angle-axis with |w| <= pi, then translation) in fp32 on p
 
 Forward (csrc/pnp.hip hrp_pnp_solve): one launch for the batch.  EPnP gives the start (the reference's cv2.solvePnP SOLVEPNP_EPNP,
 BPnP.py:36, 140), or ``ini_pose`` does (:142-145); Levenberg-Marquardt on the reprojection error then refines it (SOLVEPNP_ITERATIVE
-with useExtrinsicGuess, :41, 146).  ``BPnP_fast`` starts from the same EPnP solution: the reference's RANSAC start
-(cv2.solvePnPRansac, :266) is not built.
+with useExtrinsicGuess, :41, 146).  ``BPnP_fast`` starts from the same EPnP solution.
+Robust forward (hrp_pnp_solve_robust, ``pnp_solve_robust`` / ``BPnP_robust``): the reference's RANSAC start (cv2.solvePnPRansac with
+reprojectionError = 3, :267) as one launch: consensus over P3P hypotheses, then the same LM on the inliers, refitted while the inlier set
+changes; ``refine_all`` adds the LM over all points that BPnP_fast runs from there (:268-271).  It differs from cv2 in two ways, so
+parity is by objective, not by bits: the minimal sets are enumerated (every triple, or a fixed hash-drawn list of ``max_hypotheses``
+triples where there are more), not sampled until a confidence is reached, and each is solved by P3P, not by five-point EPnP.  The
+result is deterministic.  Its backward is the gradient below restricted to the inliers (hrp_pnp_bwd_masked), or BPnP_fast's over all
+points with ``refine_all``.
 Backward (hrp_pnp_bwd): the reference's formula, -g^T J_fy^-1 J_f(x, z, K) (:50-111, 154-236), with the derivatives of get_coefs'
 coefficients kept, or dropped for ``BPnP_fast`` (:280-341).  The forward's rotation is the exact Rodrigues formula (cv2's); the
 backward differentiates the rotation the reference's backward uses (kornia's: axis = w / (theta + 1e-6), first-order below
@@ -80,6 +86,55 @@ def pnp_backward(pts2d, pts3d, K, P_6d, grad_output, fast=False, shared=None):
     return gx, (gz_sum if shared else gz), (gK_sum if k_shared else gK), status
 
 
+def pnp_solve_robust(pts2d, pts3d, K, reproj_error=3.0, valid=None, min_inliers=4, max_hypotheses=1024, seed=0, refine_all=False):
+    """Consensus over P3P hypotheses, then LM on the inliers (and over all usable points with ``refine_all``): P_6d [B,6], inliers
+    [B,n] bool (the points within ``reproj_error`` px of P_6d), status [B,4] int32 (HRP_PNP_* flags, LM trials, inlier count,
+    hypotheses scored) and rms [B] over the points of the last fit.  ``valid`` [B,n] marks the usable points; a point with a
+    non-finite coordinate is unusable too.  Below ``min_inliers`` the flag _native.PNP_NO_CONSENSUS is set and P_6d is ``pnp_solve``'s
+    over the usable points.  No autograd, no synchronisation: graph-capturable."""
+    shared = pts3d.dim() == 2
+    _check(pts2d, pts3d, K, None, shared)
+    B, n = pts2d.shape[0], pts2d.shape[1]
+    dev = pts2d.device
+    x, z, k = _f32(pts2d), _f32(pts3d), _f32(K)
+    v = None
+    if valid is not None:
+        if tuple(valid.shape) != (B, n):
+            raise ValueError(f"BPnP: valid must be [{B}, {n}], got {list(valid.shape)}")
+        v = (valid.to(dev) != 0).to(torch.uint8).contiguous()
+    P = torch.empty(B, 6, device=dev)
+    inl = torch.empty(B, n, dtype=torch.uint8, device=dev)
+    status = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    rms = torch.empty(B, device=dev)
+    nv.call("hrp_pnp_solve_robust", x.data_ptr(), z.data_ptr(), 0 if shared else 3 * n, k.data_ptr(), 0 if k.dim() == 2 else 9,
+            v.data_ptr() if v is not None else None, B, n, float(reproj_error), int(min_inliers), int(max_hypotheses), int(seed),
+            int(bool(refine_all)), P.data_ptr(), inl.data_ptr(), status.data_ptr(), rms.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    return P, inl.bool(), status, rms
+
+
+def pnp_backward_masked(pts2d, pts3d, K, P_6d, grad_output, mask, fast=False, shared=None):
+    """``pnp_backward`` over the points of ``mask`` [B,n]: the others contribute nothing and get zero grad_x / grad_z rows."""
+    if shared is None:
+        shared = pts3d.dim() == 2
+    B, n = pts2d.shape[0], pts2d.shape[1]
+    dev = pts2d.device
+    x, z, k, P, g = _f32(pts2d), _f32(pts3d), _f32(K), _f32(P_6d), _f32(grad_output)
+    m = (mask.to(dev) != 0).to(torch.uint8).contiguous()
+    k_shared = k.dim() == 2
+    gx = torch.empty(B, n, 2, device=dev)
+    gz = torch.empty(B, n, 3, device=dev)
+    gK = torch.empty(B, 3, 3, device=dev)
+    gz_sum = torch.empty(n, 3, device=dev) if shared else None
+    gK_sum = torch.empty(3, 3, device=dev) if k_shared else None
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    nv.call("hrp_pnp_bwd_masked", x.data_ptr(), z.data_ptr(), 0 if shared else 3 * n, k.data_ptr(), 0 if k_shared else 9, P.data_ptr(),
+            g.data_ptr(), m.data_ptr(), B, n, int(fast), gx.data_ptr(), gz.data_ptr(), gK.data_ptr(),
+            gz_sum.data_ptr() if shared else None, gK_sum.data_ptr() if k_shared else None, status.data_ptr(),
+            torch.cuda.current_stream(dev).cuda_stream)
+    return gx, (gz_sum if shared else gz), (gK_sum if k_shared else gK), status
+
+
 def _forward(ctx, shared, pts2d, pts3d, K, ini_pose):
     _check(pts2d, pts3d, K, ini_pose, shared)
     P_6d, _, _ = pnp_solve(pts2d, pts3d, K, ini_pose, shared=shared)
@@ -118,7 +173,7 @@ class BPnP_m3d(torch.autograd.Function):
 
 
 class BPnP_fast(torch.autograd.Function):
-    """BPnP with the coefficient derivatives dropped from the backward (BPnP.py:239-341); EPnP start instead of RANSAC."""
+    """BPnP with the coefficient derivatives dropped from the backward (BPnP.py:239-341); EPnP start (the RANSAC start: BPnP_robust)."""
 
     @staticmethod
     def forward(ctx, pts2d, pts3d, K, ini_pose=None):
@@ -127,6 +182,29 @@ class BPnP_fast(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         return _backward(ctx, True, True, grad_output)
+
+
+class BPnP_robust(torch.autograd.Function):
+    """``pnp_solve_robust`` with a backward; pts3d [n, 3] shared or [B, n, 3].  ``BPnP_robust.apply(...)`` returns (P_6d, inliers [B, n]
+    bool, not differentiable).  refine_all=False: the implicit-function gradient at the optimum over the inliers (outliers get zero
+    rows).  refine_all=True: BPnP_fast's backward over all points (BPnP.py:280-341)."""
+
+    @staticmethod
+    def forward(ctx, pts2d, pts3d, K, reproj_error=3.0, refine_all=False):
+        P_6d, inliers, _, _ = pnp_solve_robust(pts2d, pts3d, K, reproj_error=reproj_error, refine_all=refine_all)
+        ctx.save_for_backward(pts2d, P_6d, pts3d, K, inliers)
+        ctx.refine_all = bool(refine_all)
+        ctx.mark_non_differentiable(inliers)
+        return P_6d, inliers
+
+    @staticmethod
+    def backward(ctx, grad_output, _grad_inliers=None):
+        pts2d, P_6d, pts3d, K, inliers = ctx.saved_tensors
+        if ctx.refine_all:
+            gx, gz, gK, _ = pnp_backward(pts2d, pts3d, K, P_6d, grad_output, fast=True)
+        else:
+            gx, gz, gK, _ = pnp_backward_masked(pts2d, pts3d, K, P_6d, grad_output, inliers)
+        return gx.to(pts2d.dtype), gz.to(pts3d.dtype), gK.to(K.dtype), None, None
 
 
 def batch_project(P, pts3d, K, angle_axis=True):

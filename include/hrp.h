@@ -45,6 +45,9 @@
  *                                                     lib/utils/BPnP.py:24-47, 129-151, 255-278
  *   hrp_pnp_bwd               their backward (implicit-function gradient through get_coefs)
  *                                                     lib/utils/BPnP.py:50-111, 154-236, 280-341, 344-357
+ *   hrp_pnp_solve_robust      BPnP_fast's cv2.solvePnPRansac start and refinement: consensus over P3P hypotheses, LM on the inliers
+ *                                                     lib/utils/BPnP.py:255-278 (:267-271)
+ *   hrp_pnp_bwd_masked        hrp_pnp_bwd over the points of a mask (the inliers)
  *   hrp_dream_augment         DreamDataset's colour jitter, occlusion fill and ImageEnhance.Sharpness over the working frame,
  *                             and the convert("L") sums of ImageEnhance.Contrast
  *                                                     lib/dataset/dream.py:226-255; roboutils.py:163-195; augmentations.py:96-123
@@ -892,6 +895,34 @@ int hrp_pnp_solve(const float* pts2d, const float* pts3d, int pts3d_stride, cons
 int hrp_pnp_bwd(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
                 const float* grad_out, int B, int n, int fast, float* grad_x, float* grad_z, float* grad_K, float* grad_z_sum,
                 float* grad_K_sum, int* status, void* stream);
+
+/* Robust PnP: what the reference's BPnP_fast gets from cv2.solvePnPRansac(reprojectionError, confidence) followed by solvePnP
+ * (lib/utils/BPnP.py:267-271), as one launch, one 64-lane workgroup per sample, fp64 inside, no global scratch (csrc/pnp.hip, the
+ * per-hypothesis core in csrc/pnp_minimal.h).  Unlike cv2, the minimal sets are enumerated, not drawn - all C(m, 3) triples of the m
+ * usable points in lexicographic order, or, where C(m, 3) > max_hypotheses, max_hypotheses triples from a counter-based hash of
+ * (seed, index) - and each is solved by P3P (Grunert), not by five-point EPnP: parity with cv2 is by objective, not by bits, and two
+ * calls return the same bytes.
+ *   1. lane = hypothesis, in passes of 64: P3P on the triple, every root scored against the usable points: a point is an inlier if its
+ *      camera depth is positive and its reprojection error is finite and < reproj_error px.  Score = (inliers, -sum of their squared
+ *      errors), ties to the lower hypothesis, then the lower root; a butterfly picks the winner.
+ *   2. lane = point: hrp_pnp_solve's LM on the winner's inliers from the winner's pose, re-score, refit while the set changes (three
+ *      refits at most); refine_all = 1: one more LM over all usable points from there (BPnP_fast's recipe).
+ *   valid [B,n] bytes (optional): 0 marks a point unusable; a point with a non-finite coordinate is unusable too.  Unusable points
+ *   are in no triple and never inliers.  Other arguments as hrp_pnp_solve; 4 <= min_inliers <= 64, 1 <= max_hypotheses <= 2^20.
+ *   P6d [B,6]; inliers [B,n] bytes: the points within reproj_error of P6d; rms [B] over the points of the last fit;
+ *   status [B,4] = (HRP_PNP_* flags, LM trials, inlier count, hypotheses scored).
+ * If the best consensus is below min_inliers, HRP_PNP_NO_CONSENSUS is set and P6d, rms are what hrp_pnp_solve gives for the usable
+ * points (EPnP + LM; the same bits where all points are usable).  HRP_PNP_FEW_POINTS: fewer than 4 usable points; no hypothesis is
+ * formed, both flags are set and P6d is not meaningful.  HRP_PNP_CONVERGED: the last LM ended before its trial cap.
+ * hrp_pnp_bwd_masked is hrp_pnp_bwd with mask [B,n] bytes: a point whose byte is 0 contributes nothing to J_fy, J_fz, J_fK and gets
+ * zero grad_x / grad_z (the implicit-function gradient at the optimum over the inliers). */
+enum { HRP_PNP_NO_CONSENSUS = 1, HRP_PNP_CONVERGED = 2, HRP_PNP_FEW_POINTS = 4 };
+int hrp_pnp_solve_robust(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride,
+                         const unsigned char* valid, int B, int n, double reproj_error, int min_inliers, int max_hypotheses,
+                         unsigned seed, int refine_all, float* P6d, unsigned char* inliers, int* status, float* rms, void* stream);
+int hrp_pnp_bwd_masked(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
+                       const float* grad_out, const unsigned char* mask, int B, int n, int fast, float* grad_x, float* grad_z,
+                       float* grad_K, float* grad_z_sum, float* grad_K_sum, int* status, void* stream);
 
 /* DREAM dataset pixel work (csrc/dream.hip): the host (lib/dataset/dream.py) draws every random number and computes the geometry
  * of each sample into one hrp_dream_sample; these two launches do the per-pixel steps of a batch, bit-exact with the reference's
