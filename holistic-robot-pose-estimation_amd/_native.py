@@ -299,6 +299,7 @@ class JpegSegment(C.Structure):   # hrp_jpeg_segment
 TRACK_NO_ESTIMATE, TRACK_BAD_BOX, TRACK_LOST_OUT = 1, 2, 4             # HRP_TRACK_*
 TRACK_BBOX_EXTENDED, TRACK_BBOX_ORIGIN, TRACK_BBOX_STRICT = 0, 1, 2    # HRP_TRACK_BBOX_*
 PNP_NO_CONSENSUS, PNP_CONVERGED, PNP_FEW_POINTS = 1, 2, 4                # HRP_PNP_*
+PNP_POOLED_MAX_N, PNP_POOLED_REFITS = 16384, 8                          # HRP_PNP_POOLED_*
 TRACK_MAX_KP, TRACK_MAX_SIZE = 32, 4096
 SEED_SKIPPED, SEED_TAKEN, SEED_REFUSED = 1, 2, 4                        # HRP_SEED_*
 VERIFY_SKIPPED, VERIFY_KEPT, VERIFY_UNDECIDED, VERIFY_DROPPED = 1, 2, 4, 8    # HRP_VERIFY_*
@@ -410,6 +411,8 @@ PROTOTYPES = {
     "hrp_pnp_bwd": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "hrp_pnp_solve_robust": [_P, _P, _I, _P, _I, _P, _I, _I, C.c_double, _I, _I, C.c_uint32, _I, _P, _P, _P, _P, _P],
     "hrp_pnp_bwd_masked": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "hrp_pnp_pooled_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_size_t)],
+    "hrp_pnp_solve_pooled": [_P, _P, _P, _I, _P, _I, _I, C.c_double, _I, _I, C.c_uint32, _I, _P, _Z, _P, _P, _P, _P, _P, _P],
     "hrp_dream_augment": [_P, _I, _I, _I, _P, _P, _L, _I, _I, _P, _L, _P, _P],
     "hrp_dream_crop_resize": [_P, _L, _P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P],
     "hrp_eval_batch": [C.POINTER(EvalDesc), _P],

@@ -89,6 +89,23 @@ PNPM_HD void hypothesis_triple(int h, int m, int max_hypotheses, uint32_t seed, 
   else sample_triple(seed, (uint32_t)h, m, i, j, k);
 }
 
+// The same for the pooled solver (pnp_pooled.hip), whose m reaches 16384: ncomb3 leaves int beyond m = 2344.  min(C(m, 3), cap) in 64
+// bits without forming a product above cap: of m, m - 1, m - 2 one factor gives up its 2 and one its 3, then a b c > cap is asked
+// as a b > cap / c.
+PNPM_HD int64_t ncomb3_capped(int m, int64_t cap) {
+  if (m < 3 || cap <= 0) return 0;
+  int64_t a = m, b = m - 1, c = m - 2;
+  if (a % 2 == 0) a /= 2; else b /= 2;
+  if (a % 3 == 0) a /= 3; else if (b % 3 == 0) b /= 3; else c /= 3;
+  const int64_t ab = a * b;                          // below 2^62 for every int m
+  return ab > cap / c ? cap : ab * c;
+}
+PNPM_HD int pooled_hypothesis_count(int m, int max_hypotheses) { return m < 4 ? 0 : (int)ncomb3_capped(m, max_hypotheses); }
+PNPM_HD void pooled_hypothesis_triple(int h, int m, int max_hypotheses, uint32_t seed, int& i, int& j, int& k) {
+  if (ncomb3_capped(m, (int64_t)max_hypotheses + 1) <= max_hypotheses) unrank_triple(h, m, i, j, k);
+  else sample_triple(seed, (uint32_t)h, m, i, j, k);
+}
+
 // ---- small algebra -------------------------------------------------------------------------------------------------------------------
 PNPM_HD double dot3(const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 PNPM_HD void cross3(const double (&a)[3], const double (&b)[3], double (&c)[3]) {

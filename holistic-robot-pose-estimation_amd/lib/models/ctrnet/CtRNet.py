@@ -6,6 +6,8 @@ wrapper (the reference's checkpoints carry the ``module.`` prefix), the detectio
 * ``inference_batch_images`` / ``inference_single_image`` (49-89): the same, plus ``cTr`` from the GPU PnP solver (``BPnP_m3d`` /
   ``BPnP``, lib/utils/BPnP.py, csrc/pnp.hip - the reference calls OpenCV on the host), or, with ``reproj_error`` given, from the
   robust solver (``BPnP_robust``: consensus over P3P hypotheses, LM on the inliers), the inlier mask kept as ``last_inliers``;
+* ``inference_sequence``: ONE pose for a whole batch of frames of a fixed camera (``pnp_solve_pooled``, csrc/pnp_pooled.hip), where the
+  reference has only the per-frame calls above;
 * ``cTr_to_pose_matrix`` (114-124), ``to_valid_R_batch`` (126-129).
 
 Not built: ``render_single_robot_mask`` and ``train_on_batch`` (131-194; training the key-point network is out of scope)."""
@@ -16,7 +18,7 @@ import numpy as np
 import torch
 
 from hrpe_amd import _native as nv
-from hrpe_amd.lib.utils.BPnP import BPnP, BPnP_m3d, BPnP_robust
+from hrpe_amd.lib.utils.BPnP import BPnP, BPnP_m3d, BPnP_robust, pnp_solve_pooled
 from hrpe_amd.lib.utils.geometries import angle_axis_to_rotation_matrix
 from .keypoint_seg_resnet import KeyPointSegNet
 
@@ -108,6 +110,18 @@ class CtRNet(torch.nn.Module):
             cTr = self._robust_pose(points_2d, pts, reproj_error)
         else:
             cTr = BPnP.apply(points_2d, pts.to(points_2d.device), self.K)
+        return cTr, points_2d, torch.sigmoid(segmentation)
+
+    def inference_sequence(self, img, joint_angles, points_3d=None, reproj_error=3.0):
+        """img [F, 3, H, W] of a camera that does not move, joint_angles [F, dof] -> (cTr [1, 6]: one pose from all F x k key-points
+        through the pooled robust solver, points_2d [F, k, 2], foreground probability).  points_3d [F, k, 3]: see ``_points_3d``.
+        ``self.last_inliers`` [F, k] bool: the key-points within ``reproj_error`` px of cTr.  No gradient."""
+        points_2d, segmentation = self._seg_kp(img)
+        pts = self._points_3d(joint_angles, points_3d, True).to(points_2d.device)
+        F, k = points_2d.shape[0], points_2d.shape[1]
+        cTr, inliers, _, _, _ = pnp_solve_pooled(points_2d.reshape(1, F * k, 2), pts.reshape(1, F * k, 3), self.K,
+                                                 reproj_error=float(reproj_error), want_cov=False)
+        self.last_inliers = inliers.reshape(F, k)
         return cTr, points_2d, torch.sigmoid(segmentation)
 
     def cTr_to_pose_matrix(self, cTr):

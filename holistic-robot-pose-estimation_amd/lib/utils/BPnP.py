@@ -13,11 +13,16 @@ parity is by objective, not by bits: the minimal sets are enumerated (every trip
 triples where there are more), not sampled until a confidence is reached, and each is solved by P3P, not by five-point EPnP.  The
 result is deterministic.  Its backward is the gradient below restricted to the inliers (hrp_pnp_bwd_masked), or BPnP_fast's over all
 points with ``refine_all``.
+Pooled forward (hrp_pnp_solve_pooled, ``pnp_solve_pooled``): the robust forward's semantics for up to 16384 points per problem, three
+launches (compact, score on a grid, fit in one workgroup), with the covariance of the pose: one camera pose from all the key-points of
+a sequence (lib/core/calibrate.py).  No backward.
 Backward (hrp_pnp_bwd): the reference's formula, -g^T J_fy^-1 J_f(x, z, K) (:50-111, 154-236), with the derivatives of get_coefs'
 coefficients kept, or dropped for ``BPnP_fast`` (:280-341).  The forward's rotation is the exact Rodrigues formula (cv2's); the
 backward differentiates the rotation the reference's backward uses (kornia's: axis = w / (theta + 1e-6), first-order below
 theta^2 = 1e-6), whose ~1e-6 / theta relative difference the 6 x 6 inverse amplifies to ~2e-4 of the gradients at theta ~ 0.14.
 A singular J_fy gives NaN gradients for that sample (the reference raises in torch.inverse)."""
+import ctypes
+
 import torch
 
 from hrpe_amd import _native as nv
@@ -111,6 +116,51 @@ def pnp_solve_robust(pts2d, pts3d, K, reproj_error=3.0, valid=None, min_inliers=
             int(bool(refine_all)), P.data_ptr(), inl.data_ptr(), status.data_ptr(), rms.data_ptr(),
             torch.cuda.current_stream(dev).cuda_stream)
     return P, inl.bool(), status, rms
+
+
+def _check_pooled(pts2d, pts3d, K, valid):
+    for name, t in (("pts2d", pts2d), ("pts3d", pts3d), ("K", K)):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            raise ValueError(f"pnp_solve_pooled: {name} must be a CUDA tensor (there is no CPU path)")
+    if pts2d.dim() != 3 or pts2d.shape[2] != 2:
+        raise ValueError(f"pnp_solve_pooled: pts2d must be [B, n, 2], got {tuple(pts2d.shape)}")
+    B, n = pts2d.shape[0], pts2d.shape[1]
+    if n < 4 or n > nv.PNP_POOLED_MAX_N:
+        raise ValueError(f"pnp_solve_pooled: {n} points; the solver needs 4 <= n <= {nv.PNP_POOLED_MAX_N}")
+    if tuple(pts3d.shape) != (B, n, 3):
+        raise ValueError(f"pnp_solve_pooled: pts3d must be [{B}, {n}, 3], got {list(pts3d.shape)}")
+    if tuple(K.shape) not in ((3, 3), (B, 3, 3)):
+        raise ValueError(f"pnp_solve_pooled: K must be [3, 3] or [B, 3, 3], got {list(K.shape)}")
+    if valid is not None and tuple(valid.shape) != (B, n):
+        raise ValueError(f"pnp_solve_pooled: valid must be [{B}, {n}], got {list(valid.shape)}")
+
+
+def pnp_solve_pooled(pts2d, pts3d, K, reproj_error=3.0, valid=None, min_inliers=4, max_hypotheses=1024, seed=0, refine_all=False,
+                     want_cov=True):
+    """``pnp_solve_robust``'s consensus and refit for up to 16384 points per problem (hrp_pnp_solve_pooled, csrc/pnp_pooled.hip): the
+    solver behind one camera pose from a whole sequence.  pts2d [B,n,2], pts3d [B,n,3], K [3,3] or [B,3,3] -> P_6d [B,6], inliers
+    [B,n] bool, status [B,4] int32 (HRP_PNP_* flags, LM trials, inlier count, hypotheses scored), rms [B] over the points of the last
+    fit, and cov [B,6,6] = s^2 (J^T J)^-1 in (angle-axis, t) at P_6d over those points (None without ``want_cov``).  Below
+    ``min_inliers`` the flag _native.PNP_NO_CONSENSUS is set and P_6d is the LM over all usable points from the best hypothesis.
+    The workspace is a tensor this call owns.  No autograd, no synchronisation: graph-capturable."""
+    _check_pooled(pts2d, pts3d, K, valid)
+    B, n = pts2d.shape[0], pts2d.shape[1]
+    dev = pts2d.device
+    x, z, k = _f32(pts2d), _f32(pts3d), _f32(K)
+    v = (valid.to(dev) != 0).to(torch.uint8).contiguous() if valid is not None else None
+    need = ctypes.c_size_t(0)
+    nv.call("hrp_pnp_pooled_workspace_bytes", B, n, int(max_hypotheses), ctypes.byref(need))
+    ws = torch.empty((need.value + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    P = torch.empty(B, 6, device=dev)
+    inl = torch.empty(B, n, dtype=torch.uint8, device=dev)
+    status = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    rms = torch.empty(B, device=dev)
+    cov = torch.empty(B, 6, 6, device=dev) if want_cov else None
+    nv.call("hrp_pnp_solve_pooled", x.data_ptr(), z.data_ptr(), k.data_ptr(), 0 if k.dim() == 2 else 9,
+            v.data_ptr() if v is not None else None, B, n, float(reproj_error), int(min_inliers), int(max_hypotheses), int(seed),
+            int(bool(refine_all)), ws.data_ptr(), ws.numel() * 8, P.data_ptr(), inl.data_ptr(), status.data_ptr(), rms.data_ptr(),
+            cov.data_ptr() if want_cov else None, torch.cuda.current_stream(dev).cuda_stream)
+    return P, inl.bool(), status, rms, cov
 
 
 def pnp_backward_masked(pts2d, pts3d, K, P_6d, grad_output, mask, fast=False, shared=None):

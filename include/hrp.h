@@ -48,6 +48,8 @@
  *   hrp_pnp_solve_robust      BPnP_fast's cv2.solvePnPRansac start and refinement: consensus over P3P hypotheses, LM on the inliers
  *                                                     lib/utils/BPnP.py:255-278 (:267-271)
  *   hrp_pnp_bwd_masked        hrp_pnp_bwd over the points of a mask (the inliers)
+ *   hrp_pnp_solve_pooled      one robust pose from all the points of a sequence (fixed-camera calibration), where the reference
+ *                             solves frame by frame          scripts/test.py:121-122; lib/models/ctrnet/CtRNet.py:68-89
  *   hrp_dream_augment         DreamDataset's colour jitter, occlusion fill and ImageEnhance.Sharpness over the working frame,
  *                             and the convert("L") sums of ImageEnhance.Contrast
  *                                                     lib/dataset/dream.py:226-255; roboutils.py:163-195; augmentations.py:96-123
@@ -923,6 +925,33 @@ int hrp_pnp_solve_robust(const float* pts2d, const float* pts3d, int pts3d_strid
 int hrp_pnp_bwd_masked(const float* pts2d, const float* pts3d, int pts3d_stride, const float* K, int K_stride, const float* P6d,
                        const float* grad_out, const unsigned char* mask, int B, int n, int fast, float* grad_x, float* grad_z,
                        float* grad_K, float* grad_z_sum, float* grad_K_sum, int* status, void* stream);
+
+/* Pooled robust PnP: ONE pose from all the correspondences of a sequence (eye-to-hand calibration of a fixed camera, the multi-frame
+ * PnP of DREAM).  It replaces scripts/test.py:121-122 and CtRNet.py:68-89 applied per frame - F poses of k points each, nothing
+ * combining them - by one solve over the F x k points.  hrp_pnp_solve_robust's semantics with the point count untied from the
+ * wavefront (4 <= n <= HRP_PNP_POOLED_MAX_N), fp64 inside, three launches ordered by the kernel boundary alone (csrc/pnp_pooled.hip):
+ *   1. compact: the usable points (flag set, five finite coordinates, a finite bearing) in index order, m of them;
+ *      H = min(C(m, 3), max_hypotheses) hypotheses, 0 for m < 4: every triple of ranks in lexicographic order where C(m, 3) <=
+ *      max_hypotheses, otherwise the hash-drawn triples of (seed, h), as hrp_pnp_solve_robust.
+ *   2. score: lane = hypothesis, grid (ceil(H / 64), B); P3P on the triple, every root scored against the m points (staged through
+ *      LDS in tiles); one record (count, sum of squares, root, R, t) per hypothesis into the workspace.
+ *   3. fit: one 256-thread workgroup per problem.  The winner by (count, -sum of squares, lower hypothesis, lower root), then
+ *      hrp_pnp_solve's LM on the winner's inliers from the winner's pose, re-score, refit while the inlier set changes
+ *      (HRP_PNP_POOLED_REFITS fits at most); refine_all = 1: one more LM over all usable points.  Sums run over a thread's points in
+ *      index order, then a butterfly per wave, then the waves in order: two calls return the same bytes.
+ *   pts2d [B,n,2], pts3d [B,n,3], K and K_stride, valid, reproj_error, seed as hrp_pnp_solve_robust; 4 <= min_inliers <= n,
+ *   1 <= max_hypotheses <= 2^20.  workspace: hrp_pnp_pooled_workspace_bytes(B, n, max_hypotheses) bytes, 16-byte aligned, no
+ *   initialisation, the only scratch memory used.
+ *   P6d [B,6]; inliers [B,n] bytes: the points within reproj_error of P6d; rms [B] over the points of the last fit; status [B,4] =
+ *   (HRP_PNP_* flags, LM trials, inlier count, H).  cov [B,36] (optional): s^2 (J^T J)^-1 in (w, t) at P6d over the nfit points of
+ *   the last fit, s^2 = cost / (2 nfit - 6); all zeros with nfit <= 3 or a singular J^T J.
+ * Below min_inliers HRP_PNP_NO_CONSENSUS is set and P6d is the LM over all usable points from the winner's pose (no EPnP here: a
+ * sequence without consensus is a failed calibration).  Fewer than 4 usable points: both flags, no fit, zero P6d, rms and cov. */
+enum { HRP_PNP_POOLED_MAX_N = 16384, HRP_PNP_POOLED_REFITS = 8 };
+int hrp_pnp_pooled_workspace_bytes(int B, int n, int max_hypotheses, size_t* bytes);
+int hrp_pnp_solve_pooled(const float* pts2d, const float* pts3d, const float* K, int K_stride, const unsigned char* valid, int B, int n,
+                         double reproj_error, int min_inliers, int max_hypotheses, unsigned seed, int refine_all, void* workspace,
+                         size_t workspace_bytes, float* P6d, unsigned char* inliers, int* status, float* rms, float* cov, void* stream);
 
 /* DREAM dataset pixel work (csrc/dream.hip): the host (lib/dataset/dream.py) draws every random number and computes the geometry
  * of each sample into one hrp_dream_sample; these two launches do the per-pixel steps of a batch, bit-exact with the reference's
