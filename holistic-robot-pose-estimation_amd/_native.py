@@ -305,6 +305,8 @@ SEED_SKIPPED, SEED_TAKEN, SEED_REFUSED = 1, 2, 4                        # HRP_SE
 VERIFY_SKIPPED, VERIFY_KEPT, VERIFY_UNDECIDED, VERIFY_DROPPED = 1, 2, 4, 8    # HRP_VERIFY_*
 VERIFY_FAIL_SUPPORT, VERIFY_FAIL_COVERAGE, VERIFY_FAIL_IOU = 16, 32, 64
 TRACK_MAX_BONES, TRACK_MAX_SAMPLES = 32, 64
+KIN_CONVERGED, KIN_AT_LIMIT, KIN_FEW_ROWS, KIN_BAD_START = 1, 2, 4, 8     # HRP_KIN_*
+KIN_MAX_IT = 200                                                        # HRP_KIN_MAX_IT
 KP_STRIP_ROWS = 1                                                       # HRP_KP_STRIP_ROWS: input rows per workgroup of hrp_kp_readout_fwd
 
 
@@ -320,6 +322,15 @@ class TrackVerifyDesc(C.Structure):     # hrp_track_verify_desc
                [("bones", (C.c_int32 * 2) * TRACK_MAX_BONES), ("scale", C.c_double * 2), ("extend_ratio", C.c_double * 2),
                 ("min_support", C.c_double), ("min_coverage", C.c_double), ("min_iou", C.c_double), ("min_prob", C.c_float),
                 ("reserved", C.c_int32)]
+
+
+class KinDesc(C.Structure):     # hrp_kin_desc
+    _fields_ = [(n, C.c_void_p) for n in ("chain", "pts2d", "w2d", "pts3d", "w3d", "K")] + \
+               [("K_stride", C.c_int32), ("nkp", C.c_int32)] + [(n, C.c_void_p) for n in ("q0", "rot0", "trans0")] + \
+               [("rot_dim", C.c_int32), ("pose_stride", C.c_int32)] + [(n, C.c_void_p) for n in ("q_lo", "q_hi", "prior_q")] + \
+               [("free_q", C.c_uint32), ("free_pose", C.c_int32), ("root", C.c_int32), ("B", C.c_int32), ("dof", C.c_int32),
+                ("reserved", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("q", "rot", "trans", "xyz", "uv", "rms", "status", "cov")]
 
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
@@ -427,6 +438,7 @@ PROTOTYPES = {
     "hrp_track_update": [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "hrp_track_seed": [_P, _I, _I, C.POINTER(C.c_double), _P, _I, _I, _F, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
     "hrp_track_verify": [C.POINTER(TrackVerifyDesc), _P],
+    "hrp_kin_solve": [C.POINTER(KinDesc), _P],
     "hrp_kp_readout_pack": [_P, _I, _I, _P, _I, _P],
     "hrp_kp_readout_ws": [_I, _I],                    # returns int64 (set in lib())
     "hrp_kp_readout_fwd": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _L, _P],

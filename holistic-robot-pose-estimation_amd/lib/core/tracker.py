@@ -35,7 +35,7 @@ class PoseTracker:
     def __init__(self, model, robot, K_original, frame_hw, streams=1, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256),
                  extend_ratio=(0.2, 0.13), use_origin_bbox=False, use_extended_bbox=True, reference_keypoint_id=3, min_inside=1,
                  device=None, detector=None, detector_scale=0.5, acquire_every=0, min_support=None, min_coverage=None, min_iou=None,
-                 bones=None, verify_samples=16, verify_min_fg=16, verify_min_samples=4, verify_min_prob=0.5, renderer=None):
+                 bones=None, verify_samples=16, verify_min_fg=16, verify_min_samples=4, verify_min_prob=0.5, renderer=None, refit=None):
         """model: a callable with RootNetwithRegInt.forward's signature returning its tuple (xyz_fk last); a module is put in
         eval().  robot: its ``nkp`` (or ``link_names``) gives the number of key-points.  K_original: [3, 3] or [streams, 3, 3].
         frame_hw: (H, W) of every frame.  The bbox options select the box and K of ``k_values`` as prepare_batch does
@@ -52,7 +52,15 @@ class PoseTracker:
         verify_min_samples support samples inside the map below which support is not applied; verify_min_prob the foreground
         probability.  renderer: a RobotMeshRenderer at the detector's resolution (``robot.set_robot_renderer(K_original, frame_hw,
         scale=detector_scale)``), needed by min_iou and only by it: the silhouette of the last prediction is rendered on
-        acquisition frames."""
+        acquisition frames.
+        refit: a ``kinfit.KinematicRefit`` or None.  With one, ``step`` projects the integral head's key-points (``kp3d_int``, the
+        model's output before ``xyz_fk``) to 2-D targets, refits the model's ``(pose, rot, trans)`` to them (one more launch pair:
+        ``hrp_project_fwd``, ``hrp_kin_solve``) and tracks the refit's key-points; the KinResult is left in ``refit_result``.  In
+        "holistic" mode the targets and the solve use the crop's ``other_K``; in "fixed_camera" mode ``K_original`` (cropping changes
+        K, not the camera frame).  None: exactly the launches of a tracker without the argument."""
+        if refit is not None and not (hasattr(refit, "solve") and hasattr(refit, "mode")):
+            raise nv.HrpError("PoseTracker: refit must be a kinfit.KinematicRefit or None")
+        self.refit, self.refit_result = refit, None
         ds = tuple(detector_scale) if isinstance(detector_scale, (tuple, list)) else (detector_scale, detector_scale)
         if len(ds) != 2 or not all(np.isfinite(float(v)) and float(v) > 0 for v in ds):
             raise nv.HrpError(f"PoseTracker: detector_scale {detector_scale!r}, want one or two positive numbers")
@@ -264,6 +272,20 @@ class PoseTracker:
                 self.kp2d.data_ptr(), self.have.data_ptr(), self.kp2d_original.data_ptr(), self.status.data_ptr(), self._stream())
         return self.kp2d_original
 
+    def _refit(self, out, other_K):
+        """The model's (pose, rot, trans) refitted to its own integral key-points (out[-2], camera frame): what scripts/test.py:179
+        projects, here with the K of the view the refit works in."""
+        if len(out) < 4:
+            raise nv.HrpError("PoseTracker: a refit needs the model's kp3d_int before xyz_fk in its output")
+        from hrpe_amd.lib.utils.transforms import point_projection_from_3d_tensor
+        K = self.K_original.view(self.B, 3, 3) if self.refit.mode == "fixed_camera" else other_K
+        kp3d_int = out[-2].detach().float()
+        with torch.no_grad():
+            uv = point_projection_from_3d_tensor(K, kp3d_int)
+        res = self.refit.solve(uv, K, out[0].detach(), out[1].detach(), out[2].detach())
+        self.refit_result = res
+        return res.q, res.rot, res.trans, res.kp3d
+
     def decode(self, files):
         """A list of JPEG files' bytes -> uint8 [B, H, W, 3] on the device through dream.decode_frames: baseline files on the GPU,
         the others by Pillow.  The decode's status tensor is left in ``jpeg_status`` (jpeg.check_status reads it, and
@@ -290,8 +312,11 @@ class PoseTracker:
         p = self.prepare(frames)
         with torch.no_grad():
             out = tuple(self.model(p["reg_images"], p["root_images"], p["k_values"], p["other_K"]))
-        kp2d = self.update(out)
+        pose, rot, trans, kp3d = out[0], out[1], out[2], out[-1]
+        if self.refit is not None:
+            pose, rot, trans, kp3d = self._refit(out, p["other_K"])
+        kp2d = self.update(kp3d)
         if self.renderer is not None:
-            self._last = (out[0], out[1], out[2])                # references: what the state now is the projection of
-        return TrackResult(pose=out[0], rot=out[1], trans=out[2], kp3d=out[-1], kp2d_original=kp2d, depth=out[4] if len(out) > 4 else None, status=self.status,
+            self._last = (pose, rot, trans)                      # references: what the state now is the projection of
+        return TrackResult(pose=pose, rot=rot, trans=trans, kp3d=kp3d, kp2d_original=kp2d, depth=out[4] if len(out) > 4 else None, status=self.status,
                            k_values=self.k_values)

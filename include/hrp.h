@@ -50,6 +50,8 @@
  *   hrp_pnp_bwd_masked        hrp_pnp_bwd over the points of a mask (the inliers)
  *   hrp_pnp_solve_pooled      one robust pose from all the points of a sequence (fixed-camera calibration), where the reference
  *                             solves frame by frame          scripts/test.py:121-122; lib/models/ctrnet/CtRNet.py:68-89
+ *   hrp_kin_solve             joint angles (and the pose) from key-points by LM; nothing in the reference does this, which only
+ *                             has the `known_joint` switch          scripts/test.py
  *   hrp_dream_augment         DreamDataset's colour jitter, occlusion fill and ImageEnhance.Sharpness over the working frame,
  *                             and the convert("L") sums of ImageEnhance.Contrast
  *                                                     lib/dataset/dream.py:226-255; roboutils.py:163-195; augmentations.py:96-123
@@ -1333,6 +1335,68 @@ int64_t hrp_kp_readout_ws(int B, int Hin);
 int hrp_kp_readout_fwd(const void* x, int dtype, int B, int Hin, int Win, int Cin, int pitch, const void* packed, const float* bias,
                        int k, float lim0, float lim2, float scale_x, float scale_y, float* kp, float* ms, void* ws, int64_t ws_bytes,
                        void* stream);
+
+/* Kinematic refit: joint angles and, optionally, the camera pose from key-points by Levenberg-Marquardt (csrc/kin_core.h, host and
+ * device code; csrc/kin.hip; tests/kinfit_host_check.cpp).  It replaces nothing in the reference, which never estimates the joint
+ * state from image evidence at inference: scripts/test.py only has the `known_joint` switch that substitutes the ground truth.
+ * hrp_kin_solve is ONE launch, one 64-lane workgroup per sample, fp64 inside.  With p = (free joints ascending, then w, t when
+ * free_pose; w angle-axis) it minimises
+ *   C(p) = sum_k w2d[k] |x_k - pi(K, X_k(p))|^2                 (pixels^2)
+ *        + sum_k w3d[k] |Y_k - X_k(p)|^2                         (3-D targets in the camera frame, w3d in px^2 / m^2)
+ *        + sum_{j free} prior_q[j] (q_j - q0_j)^2                (px^2 per rad^2 or m^2)
+ *   X_k(p) = M FK_k(q),  M = [R(w) | t] for root == 0,  M = [R(w) | t] T_root(q)^-1 for root > 0 (the FK kernels' re-rooting), so a
+ *   network's rot / trans at its reference key-point go in as they are.  pi(K, X) = (K X)[:2] / (K X)[2].
+ * nkp and dof repeat the chain's counts (the chain lives on the device and the launch is sized on the host); the kernel uses the
+ * descriptor's.  rot_dim 6: two rows of R by the FK kernels' formula on input, the first two rows of R(w) on output.
+ *   LM loop      lm_refine's schedule (pnp.hip) unchanged: lambda0 = 1e-3, A = J^T J + lambda diag(J^T J), x0.1 on an accepted trial
+ *                (not below 1e-12), x10 otherwise.  It stops at an accepted step with max|step| <= 1e-12 (1 + max|p|) or at
+ *                lambda > 1e10 (both set HRP_KIN_CONVERGED), or after HRP_KIN_MAX_IT trials.
+ *   trial        clamp(p + delta) on the joint entries, to [q_lo, q_hi] (fmin(fmax(v, lo), hi): lo > hi gives hi).  The step that is
+ *                tested is the change after clamping.  A trial is accepted only if C drops; it is rejected when a used 2-D point has
+ *                camera depth X_z <= 0 or the cost is not finite, and when the damped matrix has a pivot that is not positive.
+ *   held joints  a free joint that sits on (or beyond) a bound while the descent direction -g_j points across it is held for the
+ *                trials from that linearisation: its row and column of the damped matrix are the identity's and its step is 0, so
+ *                the other parameters take the step of the problem with that joint fixed (an active set of one linearisation; without
+ *                it the clamped full step no longer lowers C next to a bounded optimum and the loop stalls short of it).  It is
+ *                released by the first linearisation whose gradient points back inside.
+ *   usable       a point is used when its weight is > 0 and its coordinates are finite (a NaN weight is not > 0).
+ *   rows         2 n2d + 3 n3d + #{free j : prior_q[j] > 0}.  With rows < npar, or npar == 0, nothing is solved:
+ *                HRP_KIN_FEW_ROWS, and q, rot, trans are the start, bit for bit.
+ *   bad start    a start with a used 2-D point at depth <= 0 or a cost that is not finite: HRP_KIN_BAD_START, outputs as the start.
+ *   at limit     HRP_KIN_AT_LIMIT when a free joint ends exactly on a bound.
+ *   rms          sqrt(sum w2d e^2 / sum w2d) over the used 2-D points at the returned parameters (0 without any).
+ *   cov          s^2 (J^T J)^-1 at the solution, J^T J including the priors, in parameter order, s^2 = C / (rows - npar); all zeros
+ *                when rows <= npar, on a pivot that is not positive, with HRP_KIN_AT_LIMIT, or when nothing was solved.
+ *   unobservable a free joint that moves no used point and has no prior makes diag(J^T J) = 0 there, the damped matrix is singular at
+ *                every lambda, every trial fails, lambda rises and the loop ends with the start: nothing undefined happens.
+ * Fixed entries are copied through bit for bit (fixed joints, and rot / trans when free_pose == 0); a returned free w has |w| <= pi.
+ * Inside, a fixed pose is used through its angle-axis vector like a free one (R(log R) is R to a few ulp of fp64).
+ * xyz / uv are the FK key-points at the returned parameters and their projection, for every key-point.  Every sum is taken in index
+ * order, so two calls return the same bytes.  dof <= HRP_FK_MAX_JOINTS and nkp <= HRP_FK_MAX_KP give npar <= 38 and at most 120
+ * residual rows in LDS (the priors are added analytically), under 64 KB.  No host synchronisation, caller-owned buffers:
+ * graph-capturable.
+ * Refused (HRP_ERR_ARG, nothing is launched): a null descriptor or required pointer (chain, pts2d, K, rot0, trans0, rot, trans,
+ * and q0, q when dof > 0), B <= 0, rot_dim not 3 or 6, nkp outside 1 .. HRP_FK_MAX_KP, dof outside 0 .. HRP_FK_MAX_JOINTS, a free_q bit at or above
+ * dof, pts3d without w3d or the reverse, K_stride not 0 or 9, pose_stride / free_pose not 0 or 1, root outside [0, nkp). */
+enum { HRP_KIN_CONVERGED = 1, HRP_KIN_AT_LIMIT = 2, HRP_KIN_FEW_ROWS = 4, HRP_KIN_BAD_START = 8 };
+#define HRP_KIN_MAX_IT 200
+typedef struct hrp_kin_desc {
+  const hrp_fk_chain* chain;              /* device */
+  const float *pts2d, *w2d;               /* [B,nkp,2]; [B,nkp] >= 0 or NULL (= 1) */
+  const float *pts3d, *w3d;               /* [B,nkp,3], [B,nkp]; both or neither */
+  const float* K; int32_t K_stride;       /* 9, or 0 = shared */
+  int32_t nkp;                            /* the chain's nkp */
+  const float* q0;                        /* [B,dof] start and prior mean */
+  const float *rot0, *trans0;             /* [B,rot_dim], [B,3]; stride 0 = one pose for all (a calibrated camera) */
+  int32_t rot_dim, pose_stride;           /* 3 angle-axis | 6 two rows of R; 1 = per sample, 0 = shared */
+  const float *q_lo, *q_hi, *prior_q;     /* [dof] each, optional */
+  uint32_t free_q; int32_t free_pose, root, B;
+  int32_t dof, reserved;                  /* the chain's dof */
+  float *q, *rot, *trans;                 /* [B,dof], [B,rot_dim], [B,3]: the solution, fixed entries copied through */
+  float *xyz, *uv;                        /* optional [B,nkp,3], [B,nkp,2] */
+  float* rms; int32_t* status; float* cov;/* [B]; [B,4] = (flags, LM trials, rows, npar); optional [B,npar,npar] */
+} hrp_kin_desc;
+int hrp_kin_solve(const hrp_kin_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

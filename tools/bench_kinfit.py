@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""Timing of the kinematic refit (lib/utils/kinfit.py, csrc/kin.hip) on the Panda at B = 1, 16, 64, 1024.
+
+Per B, device events around 30 calls after 5 warm-up calls, per call:
+  fixed_camera  ``kin_solve`` with the pose shared and fixed, the six observable joints free (npar 6), start 0.15 rad off
+  holistic      pose and joints free with prior_q = 1, root = 3 (npar 12), start 0.15 rad / 0.05 rad / 0.03 m off
+  pnp_solve     ``pnp_solve(ini_pose=...)`` on the same key-points with the joints known: the nearest thing that existed (npar 6)
+with the smallest and largest LM trial count of the batch.  The samples of a batch are seeded random configurations inside the joint
+bounds seen from about 1.5 m with +-1 px noise, so the trial counts are those of a realistic mix.  Nothing is gated on speed.
+Run on the GPU box: ``python tools/bench_kinfit.py``; prints one JSON line per B."""
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import hrpe_amd  # noqa: E402,F401
+import kinfit_oracle as ko  # noqa: E402
+from hrpe_amd.lib.dataset.const import JOINT_BOUNDS  # noqa: E402
+from hrpe_amd.lib.utils import kinfit  # noqa: E402
+from hrpe_amd.lib.utils.BPnP import pnp_solve  # noqa: E402
+from hrpe_amd.lib.utils.urdf_robot import URDFRobot  # noqa: E402
+
+DEV = torch.device("cuda:0")
+K = np.float32([[600, 0, 320], [0, 600, 240], [0, 0, 1]])
+POSE = np.array([1.2, -1.0, 0.8, 0.05, -0.1, 1.5])
+
+
+def timed_us(fn, warmup=5, reps=30):
+    for _ in range(warmup):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / reps, out
+
+
+def batch(robot, B, root):
+    """B samples: (pts2d, q_true, q0, base-frame key-points), float32 on the host; 64 distinct draws, repeated."""
+    rng = np.random.default_rng(B)
+    tab = ko.tables(robot.chain)
+    lim = np.array(JOINT_BOUNDS["panda"])
+    obs = kinfit.observable_joints(robot)
+    rows = []
+    for _ in range(min(B, 64)):
+        q = np.float32(lim[:, 0] + (0.2 + 0.6 * rng.random(8)) * (lim[:, 1] - lim[:, 0])).astype(np.float64)
+        X = ko.keypoints(tab, q, ko.rodrigues(POSE[:3]), POSE[3:], root)
+        x = ko.project(K, X) + rng.uniform(-1, 1, (7, 2))
+        q0 = np.clip(q + 0.15 * rng.standard_normal(8) * obs, lim[:, 0], lim[:, 1])
+        rows.append((x, q, q0, ko.keypoints(tab, q, np.eye(3), np.zeros(3), 0)))
+    rows = [rows[i % len(rows)] for i in range(B)]
+    return [torch.from_numpy(np.stack([r[i] for r in rows]).astype(np.float32)).to(DEV) for i in range(4)]
+
+
+def main():
+    robot = URDFRobot("panda")
+    Kd = torch.from_numpy(K).to(DEV)
+    rng = np.random.default_rng(0)
+    for B in (1, 16, 64, 1024):
+        row = dict(B=B)
+        x, q, q0, Xb = batch(robot, B, 0)
+        fixed = kinfit.KinematicRefit(robot, "fixed_camera", cTr=POSE)
+        us, res = timed_us(lambda: fixed.solve(x, Kd, q0))
+        st = res.status.cpu().numpy()
+        row.update(fixed_camera_us=round(us, 1), fixed_camera_trials=[int(st[:, 1].min()), int(st[:, 1].max())],
+                   fixed_camera_converged=int((st[:, 0] & 1).sum()))
+        x3, _, q03, _ = batch(robot, B, 3)
+        start = np.float32(POSE + np.r_[0.05 * rng.standard_normal(3), 0.03 * rng.standard_normal(3)])
+        rot = torch.from_numpy(np.float32(ko.rodrigues(start[:3].astype(np.float64))[:2].ravel())).to(DEV).repeat(B, 1)
+        trans = torch.from_numpy(start[3:]).to(DEV).repeat(B, 1)
+        hol = kinfit.KinematicRefit(robot, "holistic", prior_q=1.0)
+        us, res = timed_us(lambda: hol.solve(x3, Kd, q03, rot, trans))
+        st = res.status.cpu().numpy()
+        row.update(holistic_us=round(us, 1), holistic_trials=[int(st[:, 1].min()), int(st[:, 1].max())],
+                   holistic_converged=int((st[:, 0] & 1).sum()))
+        ini = torch.from_numpy(start).to(DEV).repeat(B, 1)
+        us, (P6, pst, rms) = timed_us(lambda: pnp_solve(x, Xb, Kd, ini_pose=ini))
+        pst = pst.cpu().numpy()
+        row.update(pnp_solve_us=round(us, 1), pnp_solve_trials=[int(pst[:, 1].min()), int(pst[:, 1].max())])
+        print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -16,7 +16,9 @@
     on a 480 x 640 one, without and with a silhouette.  The thresholds are 0, so every measurement is taken and no stream is
     dropped from one repetition to the next.
 Also: whether the model's forward synchronises (torch's sync debug mode around one call).  Prints one JSON line per B and row.
-Run on the GPU box: ``python tools/bench_track.py`` (``--acquire``: the rows of (d) only; ``--verify``: the rows of (d) and (e) only)."""
+(f) ``--refit``: ``step`` at B = 1, 4, 16 without and with a holistic kinematic refit, and the refit's LM trial counts.
+Run on the GPU box: ``python tools/bench_track.py`` (``--acquire``: the rows of (d) only; ``--verify``: the rows of (d) and (e) only;
+``--refit``: the rows of (f) only)."""
 import json
 import os
 import statistics
@@ -237,9 +239,28 @@ def bench_verify(model, robot, B, seq):
     return rows
 
 
+def bench_refit(model, robot):
+    """(f): ``step`` without and with a holistic kinematic refit (kinfit.KinematicRefit, prior_q = 1; two more launches per frame)."""
+    from hrpe_amd.lib.utils.kinfit import KinematicRefit
+    for B in (1, 4, 16):
+        seq = [torch.from_numpy(np.stack([dream_scene.texture(H, W, 10 * t + b) for b in range(B)])).to(DEV) for t in range(4)]
+        row = dict(B=B)
+        for name, refit in (("step", None), ("step_refit", KinematicRefit(robot, "holistic", prior_q=1.0))):
+            trk = PoseTracker(model, robot, K, (H, W), streams=B, device=DEV, refit=refit)
+            trk.reset(seeds(B))
+            lat, thr = wall(trk.step, seq)
+            row[name + "_latency_ms"], row[name + "_pipelined_ms"] = round(lat, 3), round(thr, 3)
+            if refit is not None:
+                st = trk.refit_result.status.cpu().numpy()
+                row["refit_flags"], row["refit_trials"] = sorted(set(int(v) for v in st[:, 0])), [int(st[:, 1].min()), int(st[:, 1].max())]
+        print(json.dumps(row), flush=True)
+
+
 def main():
     model = model_bf16()
     robot = URDFRobot("panda")
+    if "--refit" in sys.argv[1:]:
+        return bench_refit(model, robot)
     for B in (1, 4):
         seq = [torch.from_numpy(np.stack([dream_scene.texture(H, W, 10 * t + b) for b in range(B)])).to(DEV) for t in range(4)]
         print(json.dumps(bench_acquire(model, robot, B, seq)), flush=True)
