@@ -307,6 +307,8 @@ VERIFY_FAIL_SUPPORT, VERIFY_FAIL_COVERAGE, VERIFY_FAIL_IOU = 16, 32, 64
 TRACK_MAX_BONES, TRACK_MAX_SAMPLES = 32, 64
 KIN_CONVERGED, KIN_AT_LIMIT, KIN_FEW_ROWS, KIN_BAD_START = 1, 2, 4, 8     # HRP_KIN_*
 KIN_MAX_IT = 200                                                        # HRP_KIN_MAX_IT
+KF_INIT, KF_COASTED, KF_LOST, KF_BAD_START, KF_REWRAPPED, KF_CONVERGED, KF_AT_LIMIT = 1, 2, 4, 8, 16, 32, 64     # HRP_KF_*
+KIN_FILTER_MAX_N = 20                                                   # HRP_KIN_FILTER_MAX_N
 KP_STRIP_ROWS = 1                                                       # HRP_KP_STRIP_ROWS: input rows per workgroup of hrp_kp_readout_fwd
 
 
@@ -331,6 +333,16 @@ class KinDesc(C.Structure):     # hrp_kin_desc
                [("free_q", C.c_uint32), ("free_pose", C.c_int32), ("root", C.c_int32), ("B", C.c_int32), ("dof", C.c_int32),
                 ("reserved", C.c_int32)] + \
                [(n, C.c_void_p) for n in ("q", "rot", "trans", "xyz", "uv", "rms", "status", "cov")]
+
+
+class KinFilterDesc(C.Structure):     # hrp_kin_filter_desc
+    _fields_ = [(n, C.c_void_p) for n in ("chain", "pts2d", "w2d", "K")] + [("K_stride", C.c_int32), ("nkp", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("q_in", "rot_in", "trans_in")] + [("rot_dim", C.c_int32), ("pose_stride", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("q_lo", "q_hi", "w_q", "q_meas", "keep", "q_acc", "p0_var")] + \
+               [("free_q", C.c_uint32), ("free_pose", C.c_int32), ("root", C.c_int32), ("B", C.c_int32), ("dof", C.c_int32),
+                ("max_coast", C.c_int32), ("dt", C.c_double), ("gate_chi2", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("mean", "cov", "valid", "coast", "q", "rot", "trans", "xyz", "uv", "vel", "cov_p", "xyz_next", "d2",
+                                          "status")]
 
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
@@ -439,6 +451,7 @@ PROTOTYPES = {
     "hrp_track_seed": [_P, _I, _I, C.POINTER(C.c_double), _P, _I, _I, _F, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
     "hrp_track_verify": [C.POINTER(TrackVerifyDesc), _P],
     "hrp_kin_solve": [C.POINTER(KinDesc), _P],
+    "hrp_kin_filter_step": [C.POINTER(KinFilterDesc), _P],
     "hrp_kp_readout_pack": [_P, _I, _I, _P, _I, _P],
     "hrp_kp_readout_ws": [_I, _I],                    # returns int64 (set in lib())
     "hrp_kp_readout_fwd": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _L, _P],

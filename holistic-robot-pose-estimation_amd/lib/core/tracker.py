@@ -35,7 +35,8 @@ class PoseTracker:
     def __init__(self, model, robot, K_original, frame_hw, streams=1, rootnet_resize_hw=(256, 256), other_resize_hw=(256, 256),
                  extend_ratio=(0.2, 0.13), use_origin_bbox=False, use_extended_bbox=True, reference_keypoint_id=3, min_inside=1,
                  device=None, detector=None, detector_scale=0.5, acquire_every=0, min_support=None, min_coverage=None, min_iou=None,
-                 bones=None, verify_samples=16, verify_min_fg=16, verify_min_samples=4, verify_min_prob=0.5, renderer=None, refit=None):
+                 bones=None, verify_samples=16, verify_min_fg=16, verify_min_samples=4, verify_min_prob=0.5, renderer=None, filter=None,
+                 crop_from_prediction=False, refit=None):
         """model: a callable with RootNetwithRegInt.forward's signature returning its tuple (xyz_fk last); a module is put in
         eval().  robot: its ``nkp`` (or ``link_names``) gives the number of key-points.  K_original: [3, 3] or [streams, 3, 3].
         frame_hw: (H, W) of every frame.  The bbox options select the box and K of ``k_values`` as prepare_batch does
@@ -57,10 +58,27 @@ class PoseTracker:
         model's output before ``xyz_fk``) to 2-D targets, refits the model's ``(pose, rot, trans)`` to them (one more launch pair:
         ``hrp_project_fwd``, ``hrp_kin_solve``) and tracks the refit's key-points; the KinResult is left in ``refit_result``.  In
         "holistic" mode the targets and the solve use the crop's ``other_K``; in "fixed_camera" mode ``K_original`` (cropping changes
-        K, not the camera frame).  None: exactly the launches of a tracker without the argument."""
+        K, not the camera frame).  None: exactly the launches of a tracker without the argument.
+        filter: a ``kinfit.KinematicFilter`` with ``streams`` streams, or None; not together with refit.  With one, ``step`` projects
+        ``kp3d_int`` as the refit does, steps the filter with the model's ``(pose, rot, trans)`` as its inputs (``pose`` is also the
+        joints' measurement when the filter has w_q) and with a copy of ``have`` taken right after ``prepare`` as ``keep`` - a stream
+        that just lost or re-acquired its estimate starts its filter again - and tracks the filter's key-points; the
+        KinFilterResult is left in ``filter_result``.  crop_from_prediction (with a filter only): the next crop comes from the
+        filter's prediction of the next frame's key-points (``kp3d_next``, one more ``hrp_track_update``), not from this frame's,
+        which removes the one-frame lag of the crop; ``kp2d_predicted`` holds their projection.  filter=None: exactly the launches of
+        a tracker without the argument."""
         if refit is not None and not (hasattr(refit, "solve") and hasattr(refit, "mode")):
             raise nv.HrpError("PoseTracker: refit must be a kinfit.KinematicRefit or None")
+        if filter is not None and not (hasattr(filter, "step") and hasattr(filter, "mode") and hasattr(filter, "valid")):
+            raise nv.HrpError("PoseTracker: filter must be a kinfit.KinematicFilter or None")
+        if filter is not None and refit is not None:
+            raise nv.HrpError("PoseTracker: filter and refit are mutually exclusive (the filter's update is the refit with a state prior)")
+        if crop_from_prediction and filter is None:
+            raise nv.HrpError("PoseTracker: crop_from_prediction needs a filter (it is the filter that predicts)")
+        if filter is not None and int(filter.B) != int(streams):
+            raise nv.HrpError(f"PoseTracker: the filter has {filter.B} streams, the tracker {int(streams)}")
         self.refit, self.refit_result = refit, None
+        self.filter, self.filter_result, self.crop_from_prediction = filter, None, bool(crop_from_prediction)
         ds = tuple(detector_scale) if isinstance(detector_scale, (tuple, list)) else (detector_scale, detector_scale)
         if len(ds) != 2 or not all(np.isfinite(float(v)) and float(v) > 0 for v in ds):
             raise nv.HrpError(f"PoseTracker: detector_scale {detector_scale!r}, want one or two positive numbers")
@@ -128,6 +146,9 @@ class PoseTracker:
         self.seed_status = new(B, dt=torch.int32)
         self.verify_status, self.verify_counts = new(B, dt=torch.int32), new(B, 4, dt=torch.int32)
         self.verify_sums = new(B, 3, dt=torch.float64)
+        if filter is not None:
+            self._keep = new(B, dt=torch.int32)
+            self.kp2d_predicted = new(B, self.nkp, 2, dt=torch.float32)
 
     def reset(self, kp2d=None, streams=None):
         """Seed the estimate: kp2d [B, nkp, 2] in original-image pixels (float64 is kept bit for bit), or None for no estimate.
@@ -286,6 +307,25 @@ class PoseTracker:
         self.refit_result = res
         return res.q, res.rot, res.trans, res.kp3d
 
+    def _filter(self, out, other_K):
+        """The filter stepped on the model's integral key-points, with the model's (pose, rot, trans) as its inputs; ``_keep`` holds
+        ``have`` as ``prepare`` saw it."""
+        if len(out) < 4:
+            raise nv.HrpError("PoseTracker: a filter needs the model's kp3d_int before xyz_fk in its output")
+        from hrpe_amd.lib.utils.transforms import point_projection_from_3d_tensor
+        f = self.filter
+        K = self.K_original.view(self.B, 3, 3) if f.mode == "fixed_camera" else other_K
+        kp3d_int = out[-2].detach().float()
+        with torch.no_grad():
+            uv = point_projection_from_3d_tensor(K, kp3d_int)
+        pose = out[0].detach()
+        if f.mode == "fixed_camera":
+            res = f.step(uv, K, pose, keep=self._keep)
+        else:
+            res = f.step(uv, K, pose, out[1].detach(), out[2].detach(), keep=self._keep)
+        self.filter_result = res
+        return res.q, res.rot, res.trans, res.kp3d
+
     def decode(self, files):
         """A list of JPEG files' bytes -> uint8 [B, H, W, 3] on the device through dream.decode_frames: baseline files on the GPU,
         the others by Pillow.  The decode's status tensor is left in ``jpeg_status`` (jpeg.check_status reads it, and
@@ -310,12 +350,20 @@ class PoseTracker:
                 self.acquire(frames)
             self._frame += 1
         p = self.prepare(frames)
+        if self.filter is not None:
+            self._keep.copy_(self.have)
         with torch.no_grad():
             out = tuple(self.model(p["reg_images"], p["root_images"], p["k_values"], p["other_K"]))
         pose, rot, trans, kp3d = out[0], out[1], out[2], out[-1]
         if self.refit is not None:
             pose, rot, trans, kp3d = self._refit(out, p["other_K"])
+        if self.filter is not None:
+            pose, rot, trans, kp3d = self._filter(out, p["other_K"])
         kp2d = self.update(kp3d)
+        if self.crop_from_prediction:          # the state the next prepare crops from: the projection of the predicted key-points
+            nv.call("hrp_track_update", self.filter_result.kp3d_next.data_ptr(), self.K_original.data_ptr(), self.B, self.nkp, self.W, self.H,
+                    self.min_inside, self.kp2d.data_ptr(), self.have.data_ptr(), self.kp2d_predicted.data_ptr(), self.status.data_ptr(),
+                    self._stream())
         if self.renderer is not None:
             self._last = (pose, rot, trans)                      # references: what the state now is the projection of
         return TrackResult(pose=pose, rot=rot, trans=trans, kp3d=kp3d, kp2d_original=kp2d, depth=out[4] if len(out) > 4 else None, status=self.status,

@@ -12,7 +12,8 @@ Which joints CAN be solved is a property of the robot and its key-points: a join
 it moves none of them (``observable_joints``), and a joint that moves all key-points as one rigid body is absorbed by the camera pose
 when that is free too (an exact gauge).  ``kin_solve`` refuses both unless a prior (or fixing the joint) removes the freedom.  There
 is no robust loss: on this problem an outlier on a distal key-point is simply fitted by the distal joints, and a Huber loss at 3 px
-gave the L2 answer in 8 of 9 CPU experiments; the prior, the joint limits and per-point weights are what protects the estimate.
+gave the L2 answer in 8 of 9 CPU experiments; the prior, the joint limits and per-point weights are what protects the estimate -
+and, over a sequence, ``KinematicFilter`` below, whose gate knows where the arm was a frame ago.
 There is no CPU path: CPU tensors raise HrpError.  No backward."""
 import ctypes as C
 from collections import namedtuple
@@ -305,3 +306,162 @@ class KinematicRefit:
             rot, trans = c[:3], c[3:]
         return kin_solve(self.robot, pts2d, K, pose, rot, trans, free_joints=self.free, free_pose=self.free_pose, root=self.root,
                          w2d=w2d, pts3d=pts3d, w3d=w3d, prior_q=self.prior_q, limits=self.limits)
+
+
+# ---- the kinematic filter -------------------------------------------------------------------------------------------------------------------
+KinFilterResult = namedtuple("KinFilterResult", "q rot trans kp3d kp2d vel cov kp3d_next status d2")
+
+
+def _positive_vector(v, n, what, strict):
+    if v is None:
+        raise nv.HrpError(f"KinematicFilter: {what} is required (a host number or [{n}]); there is no tuned default")
+    a = _host_vector(v, n, what)
+    if not np.isfinite(a).all() or ((a <= 0).any() if strict else (a < 0).any()):
+        raise nv.HrpError(f"KinematicFilter: {what} must be finite and {'> 0' if strict else '>= 0'}")
+    return a
+
+
+class KinematicFilter:
+    """``kin_solve``'s parameters tracked over frames (``hrp_kin_filter_step``, csrc/kin_filter_core.h): a constant-velocity prior on
+    (p, v), an innovation gate on the key-points and one launch per frame.  What a per-frame refit cannot do follows from the state:
+    an outlier on a distal key-point is far from where the arm was a frame ago and is gated out; a frame without key-points is
+    coasted; the covariance is written on a joint limit too.
+
+    mode is one of ``KinematicRefit``'s: "holistic" (the pose and the observable joints are free, root = reference_keypoint_id, the
+    network's ``(pose, rot, trans)`` is where a stream starts) or "fixed_camera" (``cTr`` [6] is the one fixed pose, root = 0).  A
+    gauge joint needs no prior here: the state prior regularises it.  An unobservable free joint is refused by name unless w_q
+    measures it.
+    dt: seconds per frame.  q_acc: white-noise acceleration density per parameter, (rad or m)^2 s^-4, a host number or [n];
+    p0_var: the variances a stream starts with, (p, v), a host number or [2n]; w_q: optional weight of the regressor's joints as a
+    direct measurement, rad^-2 (m^-2), a host number or [dof]; gate_chi2: None = no gate; max_coast: frames without a usable point
+    before a stream is lost.  n = free joints + 6 (holistic) <= _native.KIN_FILTER_MAX_N.  q_acc and p0_var are REQUIRED, and w_q
+    and gate_chi2 are off unless given: nothing has been tuned on a trained network (no checkpoint exists in this tree), so there
+    is no default that would pretend to be.
+    The object owns the state (``mean`` [streams, 2n] and ``cov`` [streams, 2n, 2n] float64, ``valid`` and ``coast`` int32), created
+    on the device of the first ``step``; ``reset`` clears ``valid``.  Nothing here synchronises; a step can be captured in a graph
+    after one call outside it.  The additive pose model holds away from |w| = pi (include/hrp.h)."""
+
+    def __init__(self, robot, mode, dt, q_acc, p0_var, streams=1, cTr=None, free_joints=None, limits=True, gate_chi2=None, max_coast=5,
+                 w_q=None, reference_keypoint_id=3):
+        if mode not in ("holistic", "fixed_camera"):
+            raise nv.HrpError(f"KinematicFilter: mode {mode!r}, want 'holistic' or 'fixed_camera'")
+        if mode == "holistic" and cTr is not None:
+            raise nv.HrpError("KinematicFilter: cTr belongs to mode 'fixed_camera'")
+        if mode == "fixed_camera" and cTr is None:
+            raise nv.HrpError("KinematicFilter: mode 'fixed_camera' needs cTr [6] (CalibrationResult.cTr)")
+        self.robot, self.mode, self.free_pose = robot, mode, mode == "holistic"
+        self.root = int(reference_keypoint_id) if self.free_pose else 0
+        self.dof, self.nkp = int(robot.chain.dof), int(robot.chain.nkp)
+        if not 0 <= self.root < self.nkp:
+            raise nv.HrpError(f"KinematicFilter: reference_keypoint_id {reference_keypoint_id!r}, want 0 .. {self.nkp - 1}")
+        # the gauge check does not apply (free_pose=False below): the state prior removes that freedom
+        self.free, self.w_q = resolve_free(robot, free_joints, False, w_q)
+        self.n = int(self.free.sum()) + (6 if self.free_pose else 0)
+        if not 1 <= self.n <= nv.KIN_FILTER_MAX_N:
+            raise nv.HrpError(f"KinematicFilter: {self.n} parameters, want 1 .. {nv.KIN_FILTER_MAX_N}")
+        self.dt = self._dt(dt)
+        self.q_acc = _positive_vector(q_acc, self.n, "q_acc", False)
+        self.p0_var = _positive_vector(p0_var, 2 * self.n, "p0_var", True)
+        self.gate_chi2 = 0.0 if gate_chi2 is None else float(gate_chi2)
+        if gate_chi2 is not None and not (np.isfinite(self.gate_chi2) and self.gate_chi2 > 0):
+            raise nv.HrpError(f"KinematicFilter: gate_chi2 {gate_chi2!r}, want a positive number or None (no gate)")
+        if int(max_coast) != max_coast or int(max_coast) < 0:
+            raise nv.HrpError(f"KinematicFilter: max_coast {max_coast!r}, want an integer >= 0")
+        self.max_coast, self.B = int(max_coast), int(streams)
+        if self.B < 1:
+            raise nv.HrpError(f"KinematicFilter: {streams!r} streams")
+        self.lo = self.hi = None
+        if limits is True:
+            if getattr(robot, "robot_type", None) not in JOINT_BOUNDS:
+                raise nv.HrpError("KinematicFilter: limits=True needs a robot with JOINT_BOUNDS; pass (lo, hi) or limits=False")
+            self.lo, self.hi = _bounds(robot)
+        elif limits not in (False, None):
+            self.lo, self.hi = (_host_vector(v, self.dof, "limits") for v in limits)
+        self.cTr = None
+        if cTr is not None:
+            c = cTr.detach().double().cpu().numpy() if isinstance(cTr, torch.Tensor) else np.asarray(cTr, dtype=np.float64)
+            if c.shape != (6,) or not np.isfinite(c).all():
+                raise nv.HrpError(f"KinematicFilter: cTr {c.shape}, want 6 finite numbers (angle-axis, translation)")
+            self.cTr = c
+        self.mean = self.cov = self.valid = self.coast = None
+        self._acc = self._var = None
+
+    @staticmethod
+    def _dt(dt):
+        if isinstance(dt, torch.Tensor) or not np.isfinite(float(dt)) or not float(dt) > 0:
+            raise nv.HrpError(f"KinematicFilter: dt {dt!r}, want a positive, finite host number (seconds)")
+        return float(dt)
+
+    def _state_on(self, dev):
+        if self.mean is None:
+            z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
+            self.mean, self.cov = z(self.B, 2 * self.n, dt=torch.float64), z(self.B, 2 * self.n, 2 * self.n, dt=torch.float64)
+            self.valid, self.coast = z(self.B, dt=torch.int32), z(self.B, dt=torch.int32)
+            self._acc, self._var = torch.from_numpy(self.q_acc).to(dev), torch.from_numpy(self.p0_var).to(dev)
+        elif self.mean.device != dev:
+            raise nv.HrpError(f"KinematicFilter: the state lives on {self.mean.device}, the inputs on {dev}")
+
+    def reset(self, streams=None):
+        """Clear ``valid``: the streams (all, or the given indices) start again at their next step."""
+        if self.valid is None:
+            return
+        if streams is None:
+            self.valid.zero_()
+        else:
+            self.valid.index_fill_(0, torch.as_tensor(list(streams), dtype=torch.int64).to(self.valid.device), 0)
+
+    def step(self, pts2d, K, pose, rot=None, trans=None, w2d=None, q_meas=None, keep=None, dt=None):
+        """One frame, one launch.  pts2d [B, nkp, 2]; K [3, 3] or [B, 3, 3]; pose [B, dof]: where a stream starts and the fixed joints
+        of every frame; rot [B, 3 | 6] and trans [B, 3] in holistic mode; w2d [B, nkp]: inverse variances in px^-2 (None = 1); q_meas
+        [B, dof]: the joints' measurement, read when w_q is set (None = pose); keep [B] int32: 0 starts the stream again; dt: this
+        frame's step when it differs from the constructor's.  Returns KinFilterResult(q, rot, trans, kp3d, kp2d, vel [B, n], cov
+        [B, n, n], kp3d_next (FK at p + dt v), status [B, 4] int32 = (flags _native.KF_*, LM trials, points used, points gated),
+        d2 [B, nkp]); see include/hrp.h for the exact semantics."""
+        B, dof, nkp, n = self.B, self.dof, self.nkp, self.n
+        step_dt = self.dt if dt is None else self._dt(dt)
+        if self.free_pose:
+            if rot is None or trans is None:
+                raise nv.HrpError("KinematicFilter.step: mode 'holistic' starts from the network's rot and trans")
+            if not isinstance(rot, torch.Tensor) or rot.shape[-1] not in (3, 6):
+                raise nv.HrpError("KinematicFilter.step: the rotation must be angle-axis [B, 3] or two rows of R [B, 6]")
+        elif rot is not None or trans is not None:
+            raise nv.HrpError("KinematicFilter.step: mode 'fixed_camera' takes its pose from cTr")
+        x = _dev32(pts2d, [(B, nkp, 2)], "pts2d")
+        dev = x.device
+        k = _dev32(K, [(3, 3), (B, 3, 3)], "K")
+        q = _dev32(pose, [(B, dof)], "pose")
+        if self.free_pose:
+            r = _dev32(rot, [(B, 3), (B, 6)], "rot")
+            t = _dev32(trans, [(B, 3)], "trans")
+        else:
+            c = _constant_on(self.robot, dev, self.cTr)
+            r, t = c[:3], c[3:]
+        w2 = None if w2d is None else _dev32(w2d, [(B, nkp)], "w2d")
+        qm = None
+        if self.w_q is not None:
+            qm = q if q_meas is None else _dev32(q_meas, [(B, dof)], "q_meas")
+        if keep is not None:
+            if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype != torch.int32 or tuple(keep.shape) != (B,):
+                raise nv.HrpError(f"KinematicFilter.step: keep must be an int32 GPU tensor [{B}]")
+            keep = keep.contiguous()
+        self._state_on(dev)
+        rot_dim = int(r.shape[-1])
+        consts = [None if v is None else _constant_on(self.robot, dev, v) for v in (self.lo, self.hi, self.w_q)]
+        new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)      # noqa: E731
+        res = KinFilterResult(q=new(B, dof), rot=new(B, rot_dim), trans=new(B, 3), kp3d=new(B, nkp, 3), kp2d=new(B, nkp, 2), vel=new(B, n),
+                              cov=new(B, n, n), kp3d_next=new(B, nkp, 3), status=new(B, 4, dt=torch.int32), d2=new(B, nkp))
+        ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
+        d = nv.KinFilterDesc()
+        d.chain, d.pts2d, d.w2d = self.robot.chain_on(dev).data_ptr(), x.data_ptr(), ptr(w2)
+        d.K, d.K_stride, d.nkp, d.dof = k.data_ptr(), 0 if k.dim() == 2 else 9, nkp, dof
+        d.q_in, d.rot_in, d.trans_in, d.rot_dim, d.pose_stride = q.data_ptr(), r.data_ptr(), t.data_ptr(), rot_dim, 1 if self.free_pose else 0
+        d.q_lo, d.q_hi, d.w_q = (ptr(v) for v in consts)
+        d.q_meas, d.keep, d.q_acc, d.p0_var = ptr(qm), ptr(keep), self._acc.data_ptr(), self._var.data_ptr()
+        d.free_q, d.free_pose, d.root, d.B = int(sum(1 << int(j) for j in np.flatnonzero(self.free))), 1 if self.free_pose else 0, self.root, B
+        d.max_coast, d.dt, d.gate_chi2 = self.max_coast, step_dt, self.gate_chi2
+        d.mean, d.cov, d.valid, d.coast = self.mean.data_ptr(), self.cov.data_ptr(), self.valid.data_ptr(), self.coast.data_ptr()
+        d.q, d.rot, d.trans, d.xyz, d.uv = res.q.data_ptr(), res.rot.data_ptr(), res.trans.data_ptr(), res.kp3d.data_ptr(), res.kp2d.data_ptr()
+        d.vel, d.cov_p, d.xyz_next, d.d2, d.status = (res.vel.data_ptr(), res.cov.data_ptr(), res.kp3d_next.data_ptr(), res.d2.data_ptr(),
+                                                      res.status.data_ptr())
+        nv.call("hrp_kin_filter_step", C.byref(d), torch.cuda.current_stream(dev).cuda_stream)
+        return res

@@ -1398,6 +1398,72 @@ typedef struct hrp_kin_desc {
 } hrp_kin_desc;
 int hrp_kin_solve(const hrp_kin_desc* d, void* stream);
 
+/* Kinematic filter: hrp_kin_solve's parameters tracked over frames by an iterated extended Kalman filter in information form, with a
+ * constant-velocity prior and an innovation gate (csrc/kin_filter_core.h, host and device code; csrc/kin_filter.hip;
+ * tests/kinfilter_host_check.cpp; tests/kinfilter_oracle.py is the float64 statement).  hrp_kin_filter_step is ONE launch per frame, one
+ * 64-lane workgroup per stream, fp64 inside, no atomics and no shuffles, every sum in index order: two calls from equal state return
+ * equal bytes.  No host synchronisation and caller-owned buffers: graph-capturable.
+ * State per stream, caller-owned, read and written in place: mean fp64 [B, 2n] = (p, v) with p hrp_kin_solve's parameter vector (free
+ * joints ascending, then w, t when free_pose) and v its rate per second; cov fp64 [B, 2n, 2n]; valid, coast int32 [B].
+ * n = npar, 1 .. HRP_KIN_FILTER_MAX_N.  Of cov the step reads the upper triangles of the (p, p) and (v, v) blocks and the whole (v, p)
+ * block; it writes a symmetric matrix.
+ *   start      a stream with valid == 0, or with keep[b] == 0 (keep optional), starts this frame: p from q_in / rot_in / trans_in, v = 0,
+ *              P = diag(p0_var[2n]); no prediction and no gate; HRP_KF_INIT.
+ *   predict    p- = p + dt v, v- = v, P- = F P F^T + Q, F = [[I, dt I], [0, I]], Q_i = q_acc[i] [[dt^4/4, dt^3/2], [dt^3/2, dt^2]]
+ *              (white-noise acceleration per parameter).  A = P-_pp, B = P-_vp, C = P-_vv.  A pivot of A that is not positive, a used
+ *              point at depth <= 0 at p- or a cost that is not finite there: the stream starts again from the inputs (HRP_KF_INIT).
+ *              Inputs that are not usable either: HRP_KF_BAD_START, valid = 0, q / rot / trans are the inputs bit for bit, the
+ *              state is left as it was.
+ *   usable     a point is usable when w2d > 0 and its coordinates are finite.  w2d is an inverse variance in px^-2 (NULL = 1): the
+ *              cost below has no unit.
+ *   gate       gate_chi2 > 0, streams that did not start: with H_k the 2 x n Jacobian block and r_k the residual of usable point k
+ *              at p-, S_k = H_k A H_k^T + I / w2d_k, d2_k = r_k^T S_k^-1 r_k; a point with d2_k > gate_chi2 is not used this frame.
+ *   update     p+ minimises sum_k w2d_k |x_k - pi(K, X_k(p))|^2 + sum_{j free} w_q[j] (q_j - q_meas_j)^2 + (p - p-)^T A^-1 (p - p-)
+ *              by hrp_kin_solve's loop (schedule, clamping to [q_lo, q_hi], held joints, stopping rules) from p- with its joints
+ *              clamped to the bounds (the prior's mean stays p- itself, and so does a coasted state).  w_q [dof] and
+ *              q_meas [B, dof] go together and are optional; only entries with w_q > 0 are read.  With M = J^T W J + diag(w_q) + A^-1
+ *              at p+:  A+ = M^-1, G = B A^-1, v+ = v- + G (p+ - p-), P+ = [[A+, A+ G^T], [G A+, C - G (A - A+) G^T]].  No s^2 factor;
+ *              A^-1 makes M positive definite, so the covariance is written on a joint limit too.  coast = 0.  A pivot of M that is
+ *              not positive (not finite inputs): valid = 0, HRP_KF_LOST.
+ *   coast      no usable point left after the gate: the state becomes the prediction (for a starting stream: the start), coast += 1,
+ *              HRP_KF_COASTED; with coast > max_coast, valid = 0 and HRP_KF_LOST.  The outputs are those of the prediction.
+ *   wrap       the state keeps w as the loop leaves it; only when |w| > pi it is brought back to |w| <= pi, the three rotational
+ *              rates are set to 0, their rows and columns of P to 0 with p0_var's variances on the diagonal, HRP_KF_REWRAPPED.  The
+ *              additive model p- = p + dt v of the pose holds away from |w| = pi.
+ *   fixed      q_in supplies the fixed joints every frame, rot_in / trans_in the pose when free_pose == 0 (pose_stride 0: one
+ *              calibrated camera for all streams); they are copied to the outputs bit for bit.
+ * Outputs (fp32): q, rot (rot_dim 3 | 6), trans, and optionally xyz, uv (FK key-points at p+ and their projection), vel [B, n],
+ * cov_p [B, n, n] (A+), xyz_next [B, nkp, 3] (FK at p+ + dt v+, the joints not clamped), d2 [B, nkp] (the gate statistics, NaN where
+ * none was computed), status [B, 4] = (flags, LM trials, points used, points gated).
+ * Refused (HRP_ERR_ARG, nothing is launched): what hrp_kin_solve refuses, and dt not positive or not finite, gate_chi2 NaN, n = 0 or
+ * n > HRP_KIN_FILTER_MAX_N, a null state pointer (mean, cov, valid, coast) or q_acc / p0_var, max_coast < 0, w_q without q_meas
+ * or the reverse. */
+enum {
+  HRP_KF_INIT = 1, HRP_KF_COASTED = 2, HRP_KF_LOST = 4, HRP_KF_BAD_START = 8, HRP_KF_REWRAPPED = 16, HRP_KF_CONVERGED = 32,
+  HRP_KF_AT_LIMIT = 64
+};
+#define HRP_KIN_FILTER_MAX_N 20
+typedef struct hrp_kin_filter_desc {
+  const hrp_fk_chain* chain;              /* device */
+  const float *pts2d, *w2d;               /* [B,nkp,2]; [B,nkp] inverse variances or NULL (= 1) */
+  const float* K; int32_t K_stride;       /* 9, or 0 = shared */
+  int32_t nkp;                            /* the chain's nkp */
+  const float* q_in;                      /* [B,dof] start of the free joints, value of the fixed ones */
+  const float *rot_in, *trans_in;         /* [B,rot_dim], [B,3]; stride 0 = one pose for all */
+  int32_t rot_dim, pose_stride;
+  const float *q_lo, *q_hi;               /* [dof] each, optional */
+  const float *w_q, *q_meas;              /* [dof], [B,dof]: both or neither */
+  const int32_t* keep;                    /* [B] optional: 0 = start this frame */
+  const double *q_acc, *p0_var;           /* [n], [2n] */
+  uint32_t free_q; int32_t free_pose, root, B, dof, max_coast;
+  double dt, gate_chi2;                   /* seconds; <= 0 = no gate */
+  double *mean, *cov; int32_t *valid, *coast;        /* the state */
+  float *q, *rot, *trans;                 /* [B,dof], [B,rot_dim], [B,3] */
+  float *xyz, *uv, *vel, *cov_p, *xyz_next, *d2;     /* optional */
+  int32_t* status;                        /* optional [B,4] */
+} hrp_kin_filter_desc;
+int hrp_kin_filter_step(const hrp_kin_filter_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,9 +5,13 @@ Per B, device events around 30 calls after 5 warm-up calls, per call:
   fixed_camera  ``kin_solve`` with the pose shared and fixed, the six observable joints free (npar 6), start 0.15 rad off
   holistic      pose and joints free with prior_q = 1, root = 3 (npar 12), start 0.15 rad / 0.05 rad / 0.03 m off
   pnp_solve     ``pnp_solve(ini_pose=...)`` on the same key-points with the joints known: the nearest thing that existed (npar 6)
-with the smallest and largest LM trial count of the batch.  The samples of a batch are seeded random configurations inside the joint
+with the smallest and largest LM trial count of the batch.  With ``--filter`` also, on the fixed-camera inputs:
+  filter_start   ``KinematicFilter.step`` with keep = 0 in every call: the stream starts at the same q0 as kin_solve, with the prior
+                 diag(p0_var) (0.15 rad)^2 on the joints - kin_solve's problem plus the filter's covariance algebra and xyz_next
+  filter_update  a step from a saved one-frame-old state on key-points moved as by 0.3 rad/s (gate 40, nothing gated); the state is put
+                 back before every call by two device copies, which are inside the timed region  The samples of a batch are seeded random configurations inside the joint
 bounds seen from about 1.5 m with +-1 px noise, so the trial counts are those of a realistic mix.  Nothing is gated on speed.
-Run on the GPU box: ``python tools/bench_kinfit.py``; prints one JSON line per B."""
+Run on the GPU box: ``python tools/bench_kinfit.py [--filter]``; prints one JSON line per B."""
 import json
 import os
 import sys
@@ -60,7 +64,37 @@ def batch(robot, B, root):
     return [torch.from_numpy(np.stack([r[i] for r in rows]).astype(np.float32)).to(DEV) for i in range(4)]
 
 
+def filter_rows(robot, B, x, q, q0, Kd):
+    """The two filter timings on kin_solve's fixed-camera inputs."""
+    tab = ko.tables(robot.chain)
+    obs = kinfit.observable_joints(robot)
+    flt = kinfit.KinematicFilter(robot, "fixed_camera", 1 / 30, 10.0, np.r_[np.full(6, 0.15 ** 2), np.full(6, 1.0)], streams=B, cTr=POSE,
+                                 gate_chi2=40.0)
+    zero = torch.zeros(B, dtype=torch.int32, device=DEV)
+    us, res = timed_us(lambda: flt.step(x, Kd, q0, keep=zero))
+    st = res.status.cpu().numpy()
+    row = dict(filter_start_us=round(us, 1), filter_start_trials=[int(st[:, 1].min()), int(st[:, 1].max())],
+               filter_start_converged=int((st[:, 0] & 32).sum() // 32))
+    mean, cov = flt.mean.clone(), flt.cov.clone()
+    qn = q.cpu().numpy().astype(np.float64)
+    rng = np.random.default_rng(B + 1)
+    xn = np.stack([ko.project(K, ko.keypoints(tab, qn[b] + 0.01 * obs, ko.rodrigues(POSE[:3]), POSE[3:], 0)) + rng.uniform(-1, 1, (7, 2))
+                   for b in range(min(B, 64))])
+    xn = torch.from_numpy(np.float32(xn[[b % len(xn) for b in range(B)]])).to(DEV)
+
+    def update():
+        flt.mean.copy_(mean)
+        flt.cov.copy_(cov)
+        return flt.step(xn, Kd, q0)
+    us, res = timed_us(update)
+    st = res.status.cpu().numpy()
+    row.update(filter_update_us=round(us, 1), filter_update_trials=[int(st[:, 1].min()), int(st[:, 1].max())],
+               filter_update_gated=int(st[:, 3].sum()), filter_update_converged=int((st[:, 0] & 32).sum() // 32))
+    return row
+
+
 def main():
+    with_filter = "--filter" in sys.argv[1:]
     robot = URDFRobot("panda")
     Kd = torch.from_numpy(K).to(DEV)
     rng = np.random.default_rng(0)
@@ -85,6 +119,8 @@ def main():
         us, (P6, pst, rms) = timed_us(lambda: pnp_solve(x, Xb, Kd, ini_pose=ini))
         pst = pst.cpu().numpy()
         row.update(pnp_solve_us=round(us, 1), pnp_solve_trials=[int(pst[:, 1].min()), int(pst[:, 1].max())])
+        if with_filter:
+            row.update(filter_rows(robot, B, x, q, q0, Kd))
         print(json.dumps(row), flush=True)
 
 
