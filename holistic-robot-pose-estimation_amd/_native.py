@@ -309,6 +309,7 @@ KIN_CONVERGED, KIN_AT_LIMIT, KIN_FEW_ROWS, KIN_BAD_START = 1, 2, 4, 8     # HRP_
 KIN_MAX_IT = 200                                                        # HRP_KIN_MAX_IT
 KF_INIT, KF_COASTED, KF_LOST, KF_BAD_START, KF_REWRAPPED, KF_CONVERGED, KF_AT_LIMIT = 1, 2, 4, 8, 16, 32, 64     # HRP_KF_*
 KIN_FILTER_MAX_N = 20                                                   # HRP_KIN_FILTER_MAX_N
+KS_SMOOTHED, KS_TAIL, KS_INVALID, KS_BAD_LINK, KS_CLAMPED = 1, 2, 4, 8, 16   # HRP_KS_*
 KP_STRIP_ROWS = 1                                                       # HRP_KP_STRIP_ROWS: input rows per workgroup of hrp_kp_readout_fwd
 
 
@@ -343,6 +344,19 @@ class KinFilterDesc(C.Structure):     # hrp_kin_filter_desc
                 ("max_coast", C.c_int32), ("dt", C.c_double), ("gate_chi2", C.c_double)] + \
                [(n, C.c_void_p) for n in ("mean", "cov", "valid", "coast", "q", "rot", "trans", "xyz", "uv", "vel", "cov_p", "xyz_next", "d2",
                                           "status")]
+
+
+class KinHistoryDesc(C.Structure):     # hrp_kin_history_desc
+    _fields_ = [(n, C.c_void_p) for n in ("mean", "cov", "valid", "status", "q_in", "h_mean", "h_cov", "h_valid", "h_flags", "h_dt", "h_q_in")] + \
+               [(n, C.c_int32) for n in ("B", "n", "dof", "cap", "slot", "reserved")] + [("dt", C.c_double)]
+
+
+class KinSmoothDesc(C.Structure):     # hrp_kin_smooth_desc
+    _fields_ = [(n, C.c_void_p) for n in ("chain", "mean", "cov", "valid", "flags", "dt", "q_in", "rot_fixed", "trans_fixed", "q_lo", "q_hi",
+                                          "q_acc", "gain", "link")] + \
+               [("free_q", C.c_uint32)] + [(n, C.c_int32) for n in ("free_pose", "root", "B", "dof", "nkp", "rot_dim", "cap", "first", "L",
+                                                                    "want_cov", "reserved")] + \
+               [(n, C.c_void_p) for n in ("q", "rot", "trans", "vel", "cov_p", "xyz", "status", "mean_s", "cov_s")]
 
 
 _P, _I, _F, _L, _Z = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_size_t
@@ -452,6 +466,8 @@ PROTOTYPES = {
     "hrp_track_verify": [C.POINTER(TrackVerifyDesc), _P],
     "hrp_kin_solve": [C.POINTER(KinDesc), _P],
     "hrp_kin_filter_step": [C.POINTER(KinFilterDesc), _P],
+    "hrp_kin_history_push": [C.POINTER(KinHistoryDesc), _P],
+    "hrp_kin_smooth": [C.POINTER(KinSmoothDesc), _P],
     "hrp_kp_readout_pack": [_P, _I, _I, _P, _I, _P],
     "hrp_kp_readout_ws": [_I, _I],                    # returns int64 (set in lib())
     "hrp_kp_readout_fwd": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _F, _F, _P, _P, _P, _L, _P],

@@ -14,6 +14,8 @@ when that is free too (an exact gauge).  ``kin_solve`` refuses both unless a pri
 is no robust loss: on this problem an outlier on a distal key-point is simply fitted by the distal joints, and a Huber loss at 3 px
 gave the L2 answer in 8 of 9 CPU experiments; the prior, the joint limits and per-point weights are what protects the estimate -
 and, over a sequence, ``KinematicFilter`` below, whose gate knows where the arm was a frame ago.
+Over a recorded sequence, or with a lag of a few frames, ``KinematicFilter.smooth`` / ``kin_smooth`` (``hrp_kin_smooth``,
+csrc/kin_smooth_core.h) run a Rauch-Tung-Striebel pass over the filter's posteriors: every frame then also knows its future.
 There is no CPU path: CPU tensors raise HrpError.  No backward."""
 import ctypes as C
 from collections import namedtuple
@@ -310,6 +312,8 @@ class KinematicRefit:
 
 # ---- the kinematic filter -------------------------------------------------------------------------------------------------------------------
 KinFilterResult = namedtuple("KinFilterResult", "q rot trans kp3d kp2d vel cov kp3d_next status d2")
+KinHistory = namedtuple("KinHistory", "mean cov valid flags dt q_in")
+KinSmoothResult = namedtuple("KinSmoothResult", "q rot trans vel cov kp3d status mean cov_full", defaults=(None, None))
 
 
 def _positive_vector(v, n, what, strict):
@@ -339,7 +343,14 @@ class KinematicFilter:
     is no default that would pretend to be.
     The object owns the state (``mean`` [streams, 2n] and ``cov`` [streams, 2n, 2n] float64, ``valid`` and ``coast`` int32), created
     on the device of the first ``step``; ``reset`` clears ``valid``.  Nothing here synchronises; a step can be captured in a graph
-    after one call outside it.  The additive pose model holds away from |w| = pi (include/hrp.h)."""
+    after one call outside it.  The additive pose model holds away from |w| = pi (include/hrp.h).
+    ``history`` (an attribute, 0 by default: nothing is recorded and a step issues exactly one launch): with ``flt.history = T`` the
+    filter owns a device ring of T slots (``KinHistory``: mean [T, streams, 2n] and cov [T, streams, 2n, 2n] float64, valid and flags
+    [T, streams] int32, dt [T] float64, q_in [T, streams, dof] float32) and every step is followed by one more launch,
+    ``hrp_kin_history_push``, that copies the posterior, the step's flags, its ``pose`` input and its dt into the next slot.  The slot
+    cursor lives on the host; nothing synchronises.  ``smooth`` runs the RTS pass over what is recorded, ``clear_history`` empties the
+    ring, ``reset`` starts the streams again (their next frame is INIT, which cuts the link).  A recording step and ``smooth`` raise
+    HrpError while the current stream is capturing a graph: the slot and the length would be baked into it."""
 
     def __init__(self, robot, mode, dt, q_acc, p0_var, streams=1, cTr=None, free_joints=None, limits=True, gate_chi2=None, max_coast=5,
                  w_q=None, reference_keypoint_id=3):
@@ -385,6 +396,75 @@ class KinematicFilter:
             self.cTr = c
         self.mean = self.cov = self.valid = self.coast = None
         self._acc = self._var = None
+        self._hist_cap = self._hist_len = self._hist_next = 0
+        self._hist = self._hist_rot_dim = None
+
+    @property
+    def history(self):
+        """Slots of the recorded history (0: nothing is recorded).  Setting another size empties the ring."""
+        return self._hist_cap
+
+    @history.setter
+    def history(self, slots):
+        if isinstance(slots, bool) or int(slots) != slots or int(slots) < 0:
+            raise nv.HrpError(f"KinematicFilter: history {slots!r}, want an integer >= 0")
+        if int(slots) != self._hist_cap:
+            self._hist_cap, self._hist = int(slots), None
+            self.clear_history()
+
+    def clear_history(self):
+        """Forget what was recorded (the ring's memory is kept)."""
+        self._hist_len = self._hist_next = 0
+
+    def recorded(self):
+        """(KinHistory, first, length): the ring's tensors as they lie (not copies), the slot of the oldest recorded frame and the
+        number of frames recorded: what ``kin_smooth`` takes.  (None, 0, 0) before the first recording step."""
+        if self._hist is None:
+            return None, 0, 0
+        return self._hist, (self._hist_next - self._hist_len) % self._hist_cap, self._hist_len
+
+    def _history_on(self, dev, rot_dim):
+        if self._hist is None:
+            T, B, N = self._hist_cap, self.B, 2 * self.n
+            z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=dev)      # noqa: E731
+            self._hist = KinHistory(mean=z(T, B, N, dt=torch.float64), cov=z(T, B, N, N, dt=torch.float64), valid=z(T, B, dt=torch.int32),
+                                    flags=z(T, B, dt=torch.int32), dt=z(T, dt=torch.float64), q_in=z(T, B, self.dof, dt=torch.float32))
+            self._hist_rot_dim = rot_dim
+        elif self._hist_rot_dim != rot_dim:
+            raise nv.HrpError(f"KinematicFilter: the history was recorded with rot_dim {self._hist_rot_dim}, this step has {rot_dim}")
+
+    def _push(self, q, status, step_dt, dev):
+        h = self._hist
+        d = nv.KinHistoryDesc()
+        d.mean, d.cov, d.valid, d.status, d.q_in = self.mean.data_ptr(), self.cov.data_ptr(), self.valid.data_ptr(), status.data_ptr(), q.data_ptr()
+        d.h_mean, d.h_cov, d.h_valid, d.h_flags, d.h_dt, d.h_q_in = (v.data_ptr() for v in (h.mean, h.cov, h.valid, h.flags, h.dt, h.q_in))
+        d.B, d.n, d.dof, d.cap, d.slot, d.dt = self.B, self.n, self.dof, self._hist_cap, self._hist_next, step_dt
+        nv.call("hrp_kin_history_push", C.byref(d), torch.cuda.current_stream(dev).cuda_stream)
+        self._hist_next = (self._hist_next + 1) % self._hist_cap
+        self._hist_len = min(self._hist_len + 1, self._hist_cap)
+
+    def smooth(self, lag=None, cov=True, full=False):
+        """The RTS pass over the newest ``lag`` recorded frames (None: all of them), two launches.  Returns KinSmoothResult(q [L, B, dof],
+        rot, trans, vel [L, B, n], cov [L, B, n, n] (None with cov=False), kp3d [L, B, nkp, 3], status [L, B, 2] int32 = (flags
+        _native.KS_*, later frames that reached this one), and with full=True mean [L, B, 2n] and cov_full [L, B, 2n, 2n] float64), oldest
+        frame first.  ``smooth(lag=k)`` is the last k rows of ``smooth()``, byte for byte; cov=False skips the covariance recursion
+        and leaves the other outputs' bytes as they are.  See include/hrp.h for the exact semantics."""
+        if self._hist_cap < 1:
+            raise nv.HrpError("KinematicFilter.smooth: nothing is recorded (set history = T before the steps)")
+        if self._hist_len < 1 or self._hist is None:
+            raise nv.HrpError("KinematicFilter.smooth: the history is empty")
+        L = self._hist_len if lag is None else lag
+        if isinstance(L, bool) or int(L) != L or not 1 <= int(L) <= self._hist_len:
+            raise nv.HrpError(f"KinematicFilter.smooth: lag {lag!r}, want 1 .. {self._hist_len} (the frames recorded)")
+        dev = self._hist.mean.device
+        pose = None
+        if not self.free_pose:
+            c = _constant_on(self.robot, dev, self.cTr)
+            pose = (c[:3], c[3:])
+        limits = False if self.lo is None else (self.lo, self.hi)
+        return kin_smooth(self.robot, self._hist, self.q_acc, self.free, free_pose=self.free_pose, root=self.root, pose=pose,
+                          rot_dim=self._hist_rot_dim, limits=limits, first=(self._hist_next - int(L)) % self._hist_cap, length=int(L),
+                          cov=cov, full=full)
 
     @staticmethod
     def _dt(dt):
@@ -428,6 +508,9 @@ class KinematicFilter:
             raise nv.HrpError("KinematicFilter.step: mode 'fixed_camera' takes its pose from cTr")
         x = _dev32(pts2d, [(B, nkp, 2)], "pts2d")
         dev = x.device
+        if self._hist_cap and torch.cuda.is_current_stream_capturing():
+            raise nv.HrpError("KinematicFilter.step: a step that records its history cannot be captured in a graph (the ring's slot "
+                              "would be baked into it); set history = 0 for the captured filter")
         k = _dev32(K, [(3, 3), (B, 3, 3)], "K")
         q = _dev32(pose, [(B, dof)], "pose")
         if self.free_pose:
@@ -446,6 +529,8 @@ class KinematicFilter:
             keep = keep.contiguous()
         self._state_on(dev)
         rot_dim = int(r.shape[-1])
+        if self._hist_cap:
+            self._history_on(dev, rot_dim)
         consts = [None if v is None else _constant_on(self.robot, dev, v) for v in (self.lo, self.hi, self.w_q)]
         new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)      # noqa: E731
         res = KinFilterResult(q=new(B, dof), rot=new(B, rot_dim), trans=new(B, 3), kp3d=new(B, nkp, 3), kp2d=new(B, nkp, 2), vel=new(B, n),
@@ -464,4 +549,99 @@ class KinematicFilter:
         d.vel, d.cov_p, d.xyz_next, d.d2, d.status = (res.vel.data_ptr(), res.cov.data_ptr(), res.kp3d_next.data_ptr(), res.d2.data_ptr(),
                                                       res.status.data_ptr())
         nv.call("hrp_kin_filter_step", C.byref(d), torch.cuda.current_stream(dev).cuda_stream)
+        if self._hist_cap:
+            self._push(q, res.status, step_dt, dev)
         return res
+
+
+# ---- the kinematic smoother -----------------------------------------------------------------------------------------------------------------
+def _scratch_on(robot, dev, gain, link):
+    """The links' scratch (gain fp64, link int32), kept on the robot per device and grown when a call needs more.  Calls that overlap
+    on two streams of one device would share it: smooth on one stream at a time."""
+    cache = robot.__dict__.setdefault("_kin_smooth_scratch", {})
+    g, l = cache.get(str(dev), (None, None))
+    if g is None or g.numel() < gain or l.numel() < link:
+        g = torch.empty(max(gain, 0 if g is None else g.numel()), dtype=torch.float64, device=dev)
+        l = torch.empty(max(link, 0 if l is None else l.numel()), dtype=torch.int32, device=dev)
+        cache[str(dev)] = (g, l)
+    return g, l
+
+
+def kin_smooth(robot, history, q_acc, free, *, free_pose, root=0, pose=None, rot_dim=3, limits=True, first=0, length=None, cov=True,
+               full=False):
+    """``hrp_kin_smooth`` on explicit history tensors: the Rauch-Tung-Striebel pass of ``KinematicFilter.smooth``.
+
+    history: KinHistory(mean [cap, B, 2n] and cov [cap, B, 2n, 2n] float64, valid and flags [cap, B] int32 (flags: the filter step's
+    _native.KF_*), dt [cap] float64, q_in [cap, B, dof] float32), GPU tensors, the ring as it lies: frame t = 0 .. length-1 (oldest
+    first) is slot (first + t) % cap; length None = cap.  q_acc: HOST [n], the filter's; free: HOST bool mask [dof] of the joints in
+    the state (no observability check: nothing is measured here); free_pose: the state ends with (w, t); pose: (rot [rot_dim], trans [3])
+    GPU tensors, the fixed pose when free_pose is False; rot_dim: of the rot output; limits as ``kin_solve``'s.  Returns
+    KinSmoothResult; see ``KinematicFilter.smooth`` and include/hrp.h.  Two launches, no synchronisation; raises HrpError while the
+    current stream is capturing a graph."""
+    dof, nkp = int(robot.chain.dof), int(robot.chain.nkp)
+    free = np.asarray(free)
+    if free.dtype != bool or free.shape != (dof,):
+        raise nv.HrpError(f"kin_smooth: free must be a bool mask [{dof}]")
+    n = int(free.sum()) + (6 if free_pose else 0)
+    if not 1 <= n <= nv.KIN_FILTER_MAX_N:
+        raise nv.HrpError(f"kin_smooth: {n} parameters, want 1 .. {nv.KIN_FILTER_MAX_N}")
+    acc = _host_vector(q_acc, n, "q_acc")
+    if acc is None or not np.isfinite(acc).all() or (acc < 0).any():
+        raise nv.HrpError("kin_smooth: q_acc must be finite and >= 0")
+    if not 0 <= int(root) < nkp:
+        raise nv.HrpError(f"kin_smooth: root {root!r}, want 0 .. {nkp - 1}")
+    if rot_dim not in (3, 6):
+        raise nv.HrpError(f"kin_smooth: rot_dim {rot_dim!r}, want 3 or 6")
+    lo = hi = None
+    if limits is True:
+        if getattr(robot, "robot_type", None) not in JOINT_BOUNDS:
+            raise nv.HrpError("kin_smooth: limits=True needs a robot with JOINT_BOUNDS; pass (lo, hi) or limits=False")
+        lo, hi = _bounds(robot)
+    elif limits not in (False, None):
+        lo, hi = (_host_vector(v, dof, "limits") for v in limits)
+    h = KinHistory(*history)
+    if not isinstance(h.mean, torch.Tensor) or not h.mean.is_cuda or h.mean.dim() != 3:
+        raise nv.HrpError("kin_smooth: history.mean must be a GPU tensor [cap, B, 2n] (there is no CPU path)")
+    cap, B, N = int(h.mean.shape[0]), int(h.mean.shape[1]), 2 * n
+    dev = h.mean.device
+    for name, want, dt in (("mean", (cap, B, N), torch.float64), ("cov", (cap, B, N, N), torch.float64), ("valid", (cap, B), torch.int32),
+                           ("flags", (cap, B), torch.int32), ("dt", (cap,), torch.float64), ("q_in", (cap, B, dof), torch.float32)):
+        v = getattr(h, name)
+        if not isinstance(v, torch.Tensor) or v.device != dev or v.dtype != dt or tuple(v.shape) != want or not v.is_contiguous():
+            raise nv.HrpError(f"kin_smooth: history.{name} must be a contiguous {dt} tensor {want} on {dev}")
+    L = cap if length is None else int(length)
+    if not 1 <= L <= cap or not 0 <= int(first) < cap or B < 1:
+        raise nv.HrpError(f"kin_smooth: length {length!r} / first {first!r}, want 1 <= length <= cap = {cap} and 0 <= first < cap")
+    if free_pose:
+        if pose is not None:
+            raise nv.HrpError("kin_smooth: pose is the fixed pose of free_pose=False")
+        rf = tf = None
+    else:
+        if pose is None:
+            raise nv.HrpError("kin_smooth: free_pose=False needs pose = (rot, trans)")
+        rf, tf = _dev32(pose[0], [(rot_dim,)], "pose[0]"), _dev32(pose[1], [(3,)], "pose[1]")
+    if torch.cuda.is_current_stream_capturing():
+        raise nv.HrpError("kin_smooth: cannot be captured in a graph (the ring's start and length would be baked into it)")
+    consts = [None if v is None else _constant_on(robot, dev, v) for v in (lo, hi)]
+    cache = robot.__dict__.setdefault("_kin_consts64", {})
+    key = (str(dev), acc.tobytes())
+    if key not in cache:
+        cache[key] = torch.from_numpy(acc.copy()).to(dev)
+    gain, link = _scratch_on(robot, dev, L * B * N * N, L * B)
+    new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)      # noqa: E731
+    res = KinSmoothResult(q=new(L, B, dof), rot=new(L, B, rot_dim), trans=new(L, B, 3), vel=new(L, B, n), cov=new(L, B, n, n) if cov else None,
+                          kp3d=new(L, B, nkp, 3), status=new(L, B, 2, dt=torch.int32), mean=new(L, B, N, dt=torch.float64) if full else None,
+                          cov_full=new(L, B, N, N, dt=torch.float64) if full and cov else None)
+    ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
+    d = nv.KinSmoothDesc()
+    d.chain, d.mean, d.cov, d.valid, d.flags, d.dt, d.q_in = (robot.chain_on(dev).data_ptr(), h.mean.data_ptr(), h.cov.data_ptr(),
+                                                               h.valid.data_ptr(), h.flags.data_ptr(), h.dt.data_ptr(), h.q_in.data_ptr())
+    d.rot_fixed, d.trans_fixed, d.q_lo, d.q_hi, d.q_acc = ptr(rf), ptr(tf), ptr(consts[0]), ptr(consts[1]), cache[key].data_ptr()
+    d.gain, d.link = gain.data_ptr(), link.data_ptr()
+    d.free_q, d.free_pose, d.root, d.B = int(sum(1 << int(j) for j in np.flatnonzero(free))), 1 if free_pose else 0, int(root), B
+    d.dof, d.nkp, d.rot_dim, d.cap, d.first, d.L, d.want_cov = dof, nkp, rot_dim, cap, int(first), L, 1 if cov else 0
+    d.q, d.rot, d.trans, d.vel, d.cov_p, d.xyz = (res.q.data_ptr(), res.rot.data_ptr(), res.trans.data_ptr(), res.vel.data_ptr(), ptr(res.cov),
+                                                  res.kp3d.data_ptr())
+    d.status, d.mean_s, d.cov_s = res.status.data_ptr(), ptr(res.mean), ptr(res.cov_full)
+    nv.call("hrp_kin_smooth", C.byref(d), torch.cuda.current_stream(dev).cuda_stream)
+    return res

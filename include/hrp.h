@@ -1464,6 +1464,76 @@ typedef struct hrp_kin_filter_desc {
 } hrp_kin_filter_desc;
 int hrp_kin_filter_step(const hrp_kin_filter_desc* d, void* stream);
 
+/* Kinematic smoother: a Rauch-Tung-Striebel pass over a recorded history of the filter's posteriors (csrc/kin_smooth_core.h, host and
+ * device code; csrc/kin_smooth.hip; tests/kinsmooth_host_check.cpp; tests/kinsmooth_oracle.py is the float64 statement).
+ *
+ * hrp_kin_history_push is ONE launch that copies the filter's state after a step into slot `slot` of a ring of `cap` slots: mean
+ * [cap, B, 2n] and cov [cap, B, 2n, 2n] fp64, valid and flags [cap, B] int32 (flags = status[b][0] of the step), dt [cap] fp64 (the
+ * step's dt, a kernel argument), q_in [cap, B, dof] fp32 (the step's q_in).  Refused: a null pointer, B < 1, n outside
+ * 1 .. HRP_KIN_FILTER_MAX_N, dof outside 0 .. HRP_FK_MAX_JOINTS, cap < 1, slot outside 0 .. cap - 1, dt not positive or not finite.
+ *
+ * hrp_kin_smooth reads the ring as it lies: frame t = 0 .. L-1, oldest first, is slot (first + t) % cap.  Frame t carries the
+ * posterior x+_t = mean, P+_t = cov after its step, valid_t, the step's flags_t and that step's dt_t.
+ *   frame      usable when valid_t == 1 and its mean and the diagonal of its cov are finite; otherwise HRP_KS_INVALID, its outputs are
+ *              zeros and it belongs to no segment.
+ *   link       t -> t+1 exists when both frames are usable and flags_{t+1} has none of HRP_KF_INIT, HRP_KF_BAD_START,
+ *              HRP_KF_REWRAPPED (an INIT frame took its prior from the inputs, not from t; a REWRAPPED frame's state is in another
+ *              chart of the rotation than the prediction from t).  COASTED frames link: their posterior is the prediction.
+ *              With F = [[I, dt I], [0, I]], dt = dt_{t+1}, and Q the filter's white-noise-acceleration matrix of q_acc:
+ *              x- = F x+_t, P- = F P+_t F^T + Q, G = P+_t F^T (P-)^-1 (Cholesky of P-, 2n solves).  A pivot of P- that is not
+ *              positive or not finite, or a G that is not finite, cuts the link: HRP_KS_BAD_LINK on t.
+ *   linked     x^s_t = x+_t + G (x^s_{t+1} - x-), P^s_t = P+_t + G (P^s_{t+1} - P-) G^T; HRP_KS_SMOOTHED.
+ *   tail       a usable frame without a link (the newest, or before a cut): x^s = x+, P^s = P+, HRP_KS_TAIL; mean_s / cov_s are the
+ *              history's bytes, the fp32 outputs are recomputed from the state.
+ *   outputs    the recursion runs on unclamped values.  q: a free joint is x^s clamped to [q_lo, q_hi] (HRP_KS_CLAMPED when that moved
+ *              it), a fixed joint is the frame's recorded q_in bit for bit.  rot / trans: from x^s when free_pose (a rotation beyond pi
+ *              is wrapped for output, as the filter does), else rot_fixed / trans_fixed bit for bit.  vel [n] and cov_p [n, n] (the
+ *              (p, p) block of P^s) from x^s, P^s; xyz [nkp, 3]: FK (kin_core.h's) at the output's q and pose.  No K is taken and no uv is
+ *              returned: the caller projects.  status [2] = (flags, number of later frames that reached this one through links).
+ *              Optional fp64 mean_s [L, B, 2n] (unclamped) and cov_s [L, B, 2n, 2n] (bit-symmetric).
+ *   want_cov   0 skips the covariance recursion; cov_p and cov_s are then not written and may be NULL.  The other outputs have the
+ *              same bytes either way.
+ * Outputs are [L, B, ...], oldest first.  Frame t depends on frames t .. L-1 only: smoothing the newest `lag` frames gives the last `lag`
+ * rows of smoothing everything, byte for byte.  Every sum runs in index order, no atomics, no shuffles, symmetric results are computed
+ * on one triangle and mirrored: two calls return equal bytes and a stream's bytes do not depend on B.
+ * Two launches on the caller's stream: links, grid (L, B) (P-, its factor, G and the decision into the caller's scratch gain
+ * [L, B, 2n, 2n] fp64 and link [L, B] int32), then the walk t = L-1 .. 0, grid (B).  Nothing synchronises.
+ * Refused (HRP_ERR_ARG, nothing is launched): a null required pointer (chain, the ring, q_acc, gain, link, rot, trans, vel, xyz,
+ * status; q_in and q when dof > 0; cov_p when want_cov; rot_fixed / trans_fixed when free_pose == 0), B < 1 or B > 65535, L < 1,
+ * L > cap, cap < 1, first outside 0 .. cap - 1,
+ * n outside 1 .. HRP_KIN_FILTER_MAX_N, dof outside 0 .. HRP_FK_MAX_JOINTS, nkp outside 1 .. HRP_FK_MAX_KP, a free_q bit at or above dof,
+ * root outside 0 .. nkp - 1, rot_dim not 3 or 6, free_pose not 0 or 1. */
+enum { HRP_KS_SMOOTHED = 1, HRP_KS_TAIL = 2, HRP_KS_INVALID = 4, HRP_KS_BAD_LINK = 8, HRP_KS_CLAMPED = 16 };
+typedef struct hrp_kin_history_desc {
+  const double *mean, *cov;               /* the filter's state after the step: [B,2n], [B,2n,2n] */
+  const int32_t *valid, *status;          /* [B]; the step's status [B,4] */
+  const float* q_in;                      /* [B,dof] the step's q_in */
+  double *h_mean, *h_cov;                 /* the ring */
+  int32_t *h_valid, *h_flags;
+  double* h_dt;
+  float* h_q_in;
+  int32_t B, n, dof, cap, slot, reserved;
+  double dt;
+} hrp_kin_history_desc;
+int hrp_kin_history_push(const hrp_kin_history_desc* d, void* stream);
+
+typedef struct hrp_kin_smooth_desc {
+  const hrp_fk_chain* chain;              /* device */
+  const double *mean, *cov;               /* the ring: [cap,B,2n], [cap,B,2n,2n] */
+  const int32_t *valid, *flags;           /* [cap,B] */
+  const double* dt;                       /* [cap] */
+  const float* q_in;                      /* [cap,B,dof] */
+  const float *rot_fixed, *trans_fixed;   /* [rot_dim], [3]: the pose of every frame when free_pose == 0 */
+  const float *q_lo, *q_hi;               /* [dof] each, optional */
+  const double* q_acc;                    /* [n] */
+  double* gain; int32_t* link;            /* scratch [L,B,2n,2n], [L,B] */
+  uint32_t free_q; int32_t free_pose, root, B, dof, nkp, rot_dim, cap, first, L, want_cov, reserved;
+  float *q, *rot, *trans, *vel, *cov_p, *xyz;        /* [L,B,dof], [L,B,rot_dim], [L,B,3], [L,B,n], [L,B,n,n], [L,B,nkp,3] */
+  int32_t* status;                        /* [L,B,2] */
+  double *mean_s, *cov_s;                 /* optional [L,B,2n], [L,B,2n,2n] */
+} hrp_kin_smooth_desc;
+int hrp_kin_smooth(const hrp_kin_smooth_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

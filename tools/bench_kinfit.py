@@ -11,7 +11,13 @@ with the smallest and largest LM trial count of the batch.  With ``--filter`` al
   filter_update  a step from a saved one-frame-old state on key-points moved as by 0.3 rad/s (gate 40, nothing gated); the state is put
                  back before every call by two device copies, which are inside the timed region  The samples of a batch are seeded random configurations inside the joint
 bounds seen from about 1.5 m with +-1 px noise, so the trial counts are those of a realistic mix.  Nothing is gated on speed.
-Run on the GPU box: ``python tools/bench_kinfit.py [--filter]``; prints one JSON line per B."""
+Run on the GPU box: ``python tools/bench_kinfit.py [--filter]``; prints one JSON line per B.
+
+``--smooth`` times the smoother instead (``KinematicFilter.smooth`` / ``kin_smooth``, csrc/kin_smooth.hip) and prints one JSON line
+per (case, B): the Panda with a fixed camera (n = 6) and holistic (n = 12) filtered over 256 frames of a sinusoidal motion with a
+ring of 256 slots, and a synthetic history with n = 20 on the Baxter's chain; B = 1, 16; per L = 8, 32, 256 and cov on / off the
+microseconds per call and per frame (device events, 5 + 30 calls), next to the filter step's microseconds per frame without and with
+the recording launch (events around the 256 steps of the same run; their difference is ``hrp_kin_history_push``)."""
 import json
 import os
 import sys
@@ -93,7 +99,86 @@ def filter_rows(robot, B, x, q, q0, Kd):
     return row
 
 
+def motion(robot, T, holistic, seed):
+    """T frames of a sinusoidal motion seen by the fixed camera POSE: (pts2d [T, 7, 2], q_in [T, 8], rot [T, 3], trans [T, 3]) float32."""
+    rng = np.random.default_rng(seed)
+    tab = ko.tables(robot.chain)
+    lim = np.array(JOINT_BOUNDS["panda"])
+    obs = kinfit.observable_joints(robot)
+    centre, freq, phase = lim.mean(1), rng.uniform(0.3, 0.6, 8), rng.uniform(0, 2 * np.pi, 8)
+    Rc, tc = ko.rodrigues(POSE[:3]), POSE[3:]
+    rows = []
+    for t in range(T):
+        q = centre + 0.25 * np.sin(2 * np.pi * freq * t / 30 + phase) * obs
+        x = ko.project(K, ko.keypoints(tab, q, Rc, tc, 0)) + rng.standard_normal((7, 2))
+        Troot = ko.frames(tab, q)[tab["kp_frame"][3]] if holistic else np.eye(4)
+        pose = np.r_[ko.rotvec(Rc @ Troot[:3, :3]), Rc @ Troot[:3, 3] + tc]
+        rows.append((x, q + 0.05 * rng.standard_normal(8) * obs, pose[:3], pose[3:]))
+    return [torch.from_numpy(np.float32(np.stack([r[i] for r in rows]))).to(DEV) for i in range(4)]
+
+
+def smooth_rows():
+    import kinsmooth_oracle as ks
+    T = 256
+    Kd = torch.from_numpy(K).to(DEV)
+    panda = URDFRobot("panda")
+    for case in ("panda_fixed_camera", "panda_holistic", "synthetic_n20"):
+        for B in (1, 16):
+            row = dict(case=case, B=B)
+            if case == "synthetic_n20":
+                robot, free = URDFRobot("baxter"), np.arange(15) < 14
+                hist, q_acc = ks.synthetic(20, T, 0)
+                up = lambda a: torch.from_numpy(np.ascontiguousarray(a)[:, None].repeat(B, 1)).to(DEV)      # noqa: E731
+                h = kinfit.KinHistory(up(hist["mean"]), up(hist["cov"]), up(hist["valid"]), up(hist["flags"]), torch.from_numpy(hist["dt"]).to(DEV),
+                                      torch.zeros(T, B, 15, device=DEV))
+                row["n"] = 20
+                call = lambda L, c: kinfit.kin_smooth(robot, h, q_acc, free, free_pose=True, limits=False, first=T - L, length=L, cov=c)      # noqa: E731
+            else:
+                hol = case == "panda_holistic"
+                x, q, rot, trans = motion(panda, T, hol, B)
+                rep = lambda v: v[:, None].repeat(1, B, *([1] * (v.dim() - 1))).contiguous()      # noqa: E731
+                x, q, rot, trans = rep(x), rep(q), rep(rot), rep(trans)
+                per_frame = {}
+                for slots in (0, T):
+                    if hol:
+                        flt = kinfit.KinematicFilter(panda, "holistic", 1 / 30, np.r_[np.full(6, 10.0), np.full(3, 10.0), np.full(3, 2.0)],
+                                                     np.r_[np.full(6, 0.01), np.full(3, 0.01), np.full(3, 0.0025), np.full(6, 1.0), np.full(3, 1.0),
+                                                           np.full(3, 0.25)], streams=B, gate_chi2=40.0, w_q=50.0)
+                        one = lambda t: flt.step(x[t], Kd, q[t], rot[t], trans[t])      # noqa: E731
+                    else:
+                        flt = kinfit.KinematicFilter(panda, "fixed_camera", 1 / 30, 10.0, np.r_[np.full(6, 0.01), np.full(6, 1.0)], streams=B, cTr=POSE,
+                                                     gate_chi2=40.0)
+                        one = lambda t: flt.step(x[t], Kd, q[t])      # noqa: E731
+                    flt.history = slots
+                    for t in range(5):
+                        one(t)
+                    flt.reset()
+                    flt.clear_history()
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    a.record()
+                    for t in range(T):
+                        res = one(t)
+                    b.record()
+                    torch.cuda.synchronize()
+                    per_frame[slots] = a.elapsed_time(b) * 1e3 / T
+                st = res.status.cpu().numpy()
+                row.update(n=flt.n, filter_step_us_per_frame=round(per_frame[0], 1), recording_step_us_per_frame=round(per_frame[T], 1),
+                           push_us_per_frame=round(per_frame[T] - per_frame[0], 1), last_frame_flags=sorted(set(st[:, 0].tolist())))
+                call = lambda L, c: flt.smooth(lag=L, cov=c)      # noqa: E731
+            for L in (8, 32, T):
+                for c in (True, False):
+                    us, res = timed_us(lambda: call(L, c))
+                    st = res.status.cpu().numpy()
+                    row[f"L{L}_{'cov' if c else 'mean'}_us"] = round(us, 1)
+                    row[f"L{L}_{'cov' if c else 'mean'}_us_per_frame"] = round(us / L, 2)
+                    row[f"L{L}_smoothed"] = int((st[:, 0, 0] & 1).sum())
+            print(json.dumps(row), flush=True)
+
+
 def main():
+    if "--smooth" in sys.argv[1:]:
+        return smooth_rows()
     with_filter = "--filter" in sys.argv[1:]
     robot = URDFRobot("panda")
     Kd = torch.from_numpy(K).to(DEV)
