@@ -307,6 +307,7 @@ VERIFY_FAIL_SUPPORT, VERIFY_FAIL_COVERAGE, VERIFY_FAIL_IOU = 16, 32, 64
 TRACK_MAX_BONES, TRACK_MAX_SAMPLES = 32, 64
 KIN_CONVERGED, KIN_AT_LIMIT, KIN_FEW_ROWS, KIN_BAD_START = 1, 2, 4, 8     # HRP_KIN_*
 KIN_MAX_IT = 200                                                        # HRP_KIN_MAX_IT
+KIN_MAX_VIEWS = 8                                                       # HRP_KIN_MAX_VIEWS
 KF_INIT, KF_COASTED, KF_LOST, KF_BAD_START, KF_REWRAPPED, KF_CONVERGED, KF_AT_LIMIT = 1, 2, 4, 8, 16, 32, 64     # HRP_KF_*
 KIN_FILTER_MAX_N = 20                                                   # HRP_KIN_FILTER_MAX_N
 KS_SMOOTHED, KS_TAIL, KS_INVALID, KS_BAD_LINK, KS_CLAMPED = 1, 2, 4, 8, 16   # HRP_KS_*
@@ -334,6 +335,14 @@ class KinDesc(C.Structure):     # hrp_kin_desc
                [("free_q", C.c_uint32), ("free_pose", C.c_int32), ("root", C.c_int32), ("B", C.c_int32), ("dof", C.c_int32),
                 ("reserved", C.c_int32)] + \
                [(n, C.c_void_p) for n in ("q", "rot", "trans", "xyz", "uv", "rms", "status", "cov")]
+
+
+class KinViewsDesc(C.Structure):     # hrp_kin_views_desc
+    _fields_ = [(n, C.c_void_p) for n in ("chain", "pts2d", "w2d", "K")] + [("K_stride", C.c_int32), ("nkp", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("q0", "poses")] + [("pose_stride", C.c_int32), ("V", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("q_lo", "q_hi", "prior_q")] + \
+               [("free_q", C.c_uint32), ("B", C.c_int32), ("dof", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("q", "xyz", "uv", "rms", "rms_view", "status", "used_view", "cov")]
 
 
 class KinFilterDesc(C.Structure):     # hrp_kin_filter_desc
@@ -465,6 +474,7 @@ PROTOTYPES = {
     "hrp_track_seed": [_P, _I, _I, C.POINTER(C.c_double), _P, _I, _I, _F, _P, _F, _I, _I, _I, _I, _P, _P, _P, _P],
     "hrp_track_verify": [C.POINTER(TrackVerifyDesc), _P],
     "hrp_kin_solve": [C.POINTER(KinDesc), _P],
+    "hrp_kin_solve_views": [C.POINTER(KinViewsDesc), _P],
     "hrp_kin_filter_step": [C.POINTER(KinFilterDesc), _P],
     "hrp_kin_history_push": [C.POINTER(KinHistoryDesc), _P],
     "hrp_kin_smooth": [C.POINTER(KinSmoothDesc), _P],

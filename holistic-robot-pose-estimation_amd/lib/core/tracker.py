@@ -54,7 +54,13 @@ class PoseTracker:
         probability.  renderer: a RobotMeshRenderer at the detector's resolution (``robot.set_robot_renderer(K_original, frame_hw,
         scale=detector_scale)``), needed by min_iou and only by it: the silhouette of the last prediction is rendered on
         acquisition frames.
-        refit: a ``kinfit.KinematicRefit`` or None.  With one, ``step`` projects the integral head's key-points (``kp3d_int``, the
+        refit: a ``kinfit.KinematicRefit``, a ``kinfit.MultiViewRefit`` or None.  With a MultiViewRefit the ``streams`` are its
+        ``views``: V fixed, calibrated cameras on ONE arm.  ``step`` projects each stream's ``kp3d_int`` with that stream's
+        K_original, solves the joints once over all streams (``hrp_kin_solve_views``) from the mean of the model's ``pose`` over the
+        streams, and gives every stream the same joints, its own calibrated ``(rot, trans)`` in the model's rotation representation
+        and its own camera's key-points, so each stream's next crop comes from the joint estimate as its camera sees it; the
+        KinViewsResult is left in ``refit_result``; a filter together with it raises (there is no multi-view filter).
+        With a KinematicRefit, ``step`` projects the integral head's key-points (``kp3d_int``, the
         model's output before ``xyz_fk``) to 2-D targets, refits the model's ``(pose, rot, trans)`` to them (one more launch pair:
         ``hrp_project_fwd``, ``hrp_kin_solve``) and tracks the refit's key-points; the KinResult is left in ``refit_result``.  In
         "holistic" mode the targets and the solve use the crop's ``other_K``; in "fixed_camera" mode ``K_original`` (cropping changes
@@ -68,13 +74,15 @@ class PoseTracker:
         which removes the one-frame lag of the crop; ``kp2d_predicted`` holds their projection.  filter=None: exactly the launches of
         a tracker without the argument."""
         if refit is not None and not (hasattr(refit, "solve") and hasattr(refit, "mode")):
-            raise nv.HrpError("PoseTracker: refit must be a kinfit.KinematicRefit or None")
+            raise nv.HrpError("PoseTracker: refit must be a kinfit.KinematicRefit, a kinfit.MultiViewRefit or None")
         if filter is not None and not (hasattr(filter, "step") and hasattr(filter, "mode") and hasattr(filter, "valid")):
             raise nv.HrpError("PoseTracker: filter must be a kinfit.KinematicFilter or None")
         if filter is not None and refit is not None:
             raise nv.HrpError("PoseTracker: filter and refit are mutually exclusive (the filter's update is the refit with a state prior)")
         if crop_from_prediction and filter is None:
             raise nv.HrpError("PoseTracker: crop_from_prediction needs a filter (it is the filter that predicts)")
+        if refit is not None and refit.mode == "multi_view" and int(refit.views) != int(streams):
+            raise nv.HrpError(f"PoseTracker: the refit has {refit.views} views, the tracker {int(streams)} streams (one stream per camera)")
         if filter is not None and int(filter.B) != int(streams):
             raise nv.HrpError(f"PoseTracker: the filter has {filter.B} streams, the tracker {int(streams)}")
         self.refit, self.refit_result = refit, None
@@ -299,6 +307,8 @@ class PoseTracker:
         if len(out) < 4:
             raise nv.HrpError("PoseTracker: a refit needs the model's kp3d_int before xyz_fk in its output")
         from hrpe_amd.lib.utils.transforms import point_projection_from_3d_tensor
+        if self.refit.mode == "multi_view":
+            return self._refit_views(out, point_projection_from_3d_tensor)
         K = self.K_original.view(self.B, 3, 3) if self.refit.mode == "fixed_camera" else other_K
         kp3d_int = out[-2].detach().float()
         with torch.no_grad():
@@ -306,6 +316,19 @@ class PoseTracker:
         res = self.refit.solve(uv, K, out[0].detach(), out[1].detach(), out[2].detach())
         self.refit_result = res
         return res.q, res.rot, res.trans, res.kp3d
+
+    def _refit_views(self, out, project):
+        """The streams as the views of one arm: one joint solve from every stream's integral key-points, started at the mean of the
+        model's joints over the streams; every stream then carries the same joints, its own calibrated pose and its own camera's
+        key-points."""
+        K = self.K_original.view(self.B, 3, 3)
+        with torch.no_grad():
+            uv = project(K, out[-2].detach().float())
+            q_guess = out[0].detach().float().mean(0, keepdim=True)
+        res = self.refit.solve(uv.unsqueeze(0), K, q_guess)
+        self.refit_result = res
+        rot, trans = self.refit.pose_on(uv.device, int(out[1].shape[-1]))
+        return res.q.expand(self.B, -1), rot, trans, res.kp3d[0]
 
     def _filter(self, out, other_K):
         """The filter stepped on the model's integral key-points, with the model's (pose, rot, trans) as its inputs; ``_keep`` holds

@@ -14,6 +14,8 @@ when that is free too (an exact gauge).  ``kin_solve`` refuses both unless a pri
 is no robust loss: on this problem an outlier on a distal key-point is simply fitted by the distal joints, and a Huber loss at 3 px
 gave the L2 answer in 8 of 9 CPU experiments; the prior, the joint limits and per-point weights are what protects the estimate -
 and, over a sequence, ``KinematicFilter`` below, whose gate knows where the arm was a frame ago.
+With several fixed, calibrated cameras on one arm, ``kin_solve_views`` / ``MultiViewRefit`` (``hrp_kin_solve_views``,
+csrc/kin_views_core.h) solve the joints once from all views: a second camera lowers the joint error about tenfold.
 Over a recorded sequence, or with a lag of a few frames, ``KinematicFilter.smooth`` / ``kin_smooth`` (``hrp_kin_smooth``,
 csrc/kin_smooth_core.h) run a Rauch-Tung-Striebel pass over the filter's posteriors: every frame then also knows its future.
 There is no CPU path: CPU tensors raise HrpError.  No backward."""
@@ -308,6 +310,107 @@ class KinematicRefit:
             rot, trans = c[:3], c[3:]
         return kin_solve(self.robot, pts2d, K, pose, rot, trans, free_joints=self.free, free_pose=self.free_pose, root=self.root,
                          w2d=w2d, pts3d=pts3d, w3d=w3d, prior_q=self.prior_q, limits=self.limits)
+
+
+# ---- several fixed cameras ------------------------------------------------------------------------------------------------------------------
+KinViewsResult = namedtuple("KinViewsResult", "q rms rms_view used_view status cov kp3d kp2d")
+
+
+def kin_solve_views(robot, pts2d, K, poses, q0, *, free_joints=None, w2d=None, prior_q=None, limits=True, want_cov=True):
+    """One launch (``hrp_kin_solve_views``, csrc/kin_views_core.h): LM on the free joints of every sample over the key-points seen
+    by V fixed, calibrated cameras at once, from q0.
+
+    pts2d [B, V, nkp, 2]; K [V, 3, 3] (shared over the batch) or [B, V, 3, 3]; poses [V, 6] or [B, V, 6]: camera from base, angle-axis
+    then translation, the ``cTr`` of ``CameraCalibrator.solve()``; q0 [B, dof]; free_joints: bool mask [dof] or joint indices, None =
+    ``observable_joints``; w2d [B, V, nkp] >= 0; prior_q and limits as ``kin_solve``'s.  The camera poses are fixed, so no joint is
+    a gauge here and none needs a prior for that; an unobservable free joint without a prior raises HrpError naming the joint.
+    Returns KinViewsResult(q [B, dof], rms [B] over all used points, rms_view [B, V], used_view [B, V] int32, status [B, 4] int32 =
+    (flags _native.KIN_*, LM trials, rows, npar), cov [B, npar, npar] (None with want_cov=False), kp3d [B, V, nkp, 3] camera-frame
+    key-points of every view at q, kp2d [B, V, nkp, 2]); see include/hrp.h for the exact semantics.  Does not synchronise, keeps no state
+    between calls (constants are uploaded once and cached on the robot) and can be captured in a graph after one call outside it."""
+    dof, nkp = int(robot.chain.dof), int(robot.chain.nkp)
+    free, prior = resolve_free(robot, free_joints, False, prior_q)
+    lo = hi = None
+    if limits is True:
+        if getattr(robot, "robot_type", None) not in JOINT_BOUNDS:
+            raise nv.HrpError("kin_solve_views: limits=True needs a robot with JOINT_BOUNDS; pass (lo, hi) or limits=False")
+        lo, hi = _bounds(robot)
+    elif limits not in (False, None):
+        lo, hi = (_host_vector(v, dof, "limits") for v in limits)
+    if not isinstance(pts2d, torch.Tensor) or pts2d.dim() != 4:
+        raise nv.HrpError("kin_solve_views: pts2d must be a GPU tensor [B, V, nkp, 2] (there is no CPU path)")
+    B, V = int(pts2d.shape[0]), int(pts2d.shape[1])
+    if not 1 <= V <= nv.KIN_MAX_VIEWS:
+        raise nv.HrpError(f"kin_solve_views: {V} views, want 1 .. {nv.KIN_MAX_VIEWS}")
+    x = _dev32(pts2d, [(B, V, nkp, 2)], "pts2d")
+    dev = x.device
+    k = _dev32(K, [(V, 3, 3), (B, V, 3, 3)], "K")
+    c = _dev32(poses, [(V, 6), (B, V, 6)], "poses")
+    q = _dev32(q0, [(B, dof)], "q0")
+    w2 = None if w2d is None else _dev32(w2d, [(B, V, nkp)], "w2d")
+    npar = int(free.sum())
+    consts = [None if v is None else _constant_on(robot, dev, v) for v in (lo, hi, prior)]
+    new = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)      # noqa: E731
+    res = KinViewsResult(q=new(B, dof), rms=new(B), rms_view=new(B, V), used_view=new(B, V, dt=torch.int32), status=new(B, 4, dt=torch.int32),
+                         cov=new(B, npar, npar) if want_cov else None, kp3d=new(B, V, nkp, 3), kp2d=new(B, V, nkp, 2))
+    ptr = lambda v: None if v is None else v.data_ptr()      # noqa: E731
+    d = nv.KinViewsDesc()
+    d.chain, d.pts2d, d.w2d = robot.chain_on(dev).data_ptr(), x.data_ptr(), ptr(w2)
+    d.K, d.K_stride, d.nkp, d.q0 = k.data_ptr(), 0 if k.dim() == 3 else 9, nkp, q.data_ptr()
+    d.poses, d.pose_stride, d.V = c.data_ptr(), 0 if c.dim() == 2 else 1, V
+    d.q_lo, d.q_hi, d.prior_q = (ptr(v) for v in consts)
+    d.free_q, d.B, d.dof = int(sum(1 << int(j) for j in np.flatnonzero(free))), B, dof
+    d.q, d.xyz, d.uv, d.rms, d.rms_view = res.q.data_ptr(), res.kp3d.data_ptr(), res.kp2d.data_ptr(), res.rms.data_ptr(), res.rms_view.data_ptr()
+    d.status, d.used_view, d.cov = res.status.data_ptr(), res.used_view.data_ptr(), ptr(res.cov)
+    nv.call("hrp_kin_solve_views", C.byref(d), torch.cuda.current_stream(dev).cuda_stream)
+    return res
+
+
+def _rotation_of(w):
+    th = float(np.linalg.norm(w))
+    return np.eye(3) if th < 1e-300 else _axis_rotation(w / th, th)
+
+
+class MultiViewRefit:
+    """The options of a multi-view refit, held for a stream of calls (``PoseTracker(..., streams=V, refit=...)`` or ``solve`` directly):
+    V fixed, calibrated cameras on one arm, joints only (``mode`` = "multi_view").
+
+    cTr: [V, 6] (angle-axis then translation per camera), or a list of V entries, each a ``CalibrationResult`` (its ``cTr``), a tensor
+    or 6 numbers.  prior_q, free_joints and limits as ``kin_solve_views``'; prior_q is optional - no value has been tuned.  ``views``
+    is V; ``rot3`` [V, 3], ``rot6`` [V, 6] (two rows of R) and ``trans`` [V, 3] are the cameras' poses in both of the model's rotation
+    representations, computed on the host here."""
+    mode = "multi_view"
+
+    def __init__(self, robot, cTr, prior_q=None, free_joints=None, limits=True):
+        rows = cTr if isinstance(cTr, (list, tuple)) else [cTr]
+        rows = [getattr(r, "cTr", r) for r in rows]
+        rows = [r.detach().double().cpu().numpy() if isinstance(r, torch.Tensor) else np.asarray(r, dtype=np.float64) for r in rows]
+        try:
+            c = np.concatenate([r.reshape(-1, 6) for r in rows])
+        except ValueError:
+            raise nv.HrpError("MultiViewRefit: cTr must be [V, 6] or a list of V poses of 6 numbers (angle-axis, translation)") from None
+        if not 1 <= len(c) <= nv.KIN_MAX_VIEWS:
+            raise nv.HrpError(f"MultiViewRefit: {len(c)} views, want 1 .. {nv.KIN_MAX_VIEWS}")
+        if not np.isfinite(c).all():
+            raise nv.HrpError("MultiViewRefit: cTr must be finite")
+        self.robot, self.limits, self.cTr, self.views = robot, limits, c, len(c)
+        self.free, self.prior_q = resolve_free(robot, free_joints, False, prior_q)
+        self.rot3, self.trans = c[:, :3].copy(), c[:, 3:].copy()
+        self.rot6 = np.stack([_rotation_of(w)[:2].ravel() for w in self.rot3])
+
+    def solve(self, kp2d, K, q_guess, w2d=None):
+        """kin_solve_views with the held options: kp2d [B, V, nkp, 2], K [V, 3, 3] or [B, V, 3, 3], q_guess [B, dof]."""
+        if not isinstance(q_guess, torch.Tensor) or not q_guess.is_cuda:
+            raise nv.HrpError("kin_solve: q0 must be a GPU tensor (there is no CPU path)")
+        poses = _constant_on(self.robot, q_guess.device, self.cTr.ravel()).view(self.views, 6)
+        return kin_solve_views(self.robot, kp2d, K, poses, q_guess, free_joints=self.free, w2d=w2d, prior_q=self.prior_q, limits=self.limits)
+
+    def pose_on(self, dev, rot_dim):
+        """(rot [V, rot_dim], trans [V, 3]) on the device, uploaded once."""
+        if rot_dim not in (3, 6):
+            raise nv.HrpError(f"MultiViewRefit: rotation of {rot_dim} numbers, want 3 (angle-axis) or 6 (two rows of R)")
+        rot = self.rot3 if rot_dim == 3 else self.rot6
+        return _constant_on(self.robot, dev, rot.ravel()).view(self.views, rot_dim), _constant_on(self.robot, dev, self.trans.ravel()).view(self.views, 3)
 
 
 # ---- the kinematic filter -------------------------------------------------------------------------------------------------------------------

@@ -52,6 +52,7 @@
  *                             solves frame by frame          scripts/test.py:121-122; lib/models/ctrnet/CtRNet.py:68-89
  *   hrp_kin_solve             joint angles (and the pose) from key-points by LM; nothing in the reference does this, which only
  *                             has the `known_joint` switch          scripts/test.py
+ *   hrp_kin_solve_views       hrp_kin_solve's joints from the key-points of several fixed, calibrated cameras at once
  *   hrp_dream_augment         DreamDataset's colour jitter, occlusion fill and ImageEnhance.Sharpness over the working frame,
  *                             and the convert("L") sums of ImageEnhance.Contrast
  *                                                     lib/dataset/dream.py:226-255; roboutils.py:163-195; augmentations.py:96-123
@@ -1397,6 +1398,45 @@ typedef struct hrp_kin_desc {
   float* rms; int32_t* status; float* cov;/* [B]; [B,4] = (flags, LM trials, rows, npar); optional [B,npar,npar] */
 } hrp_kin_desc;
 int hrp_kin_solve(const hrp_kin_desc* d, void* stream);
+
+/* Multi-view kinematic refit: the joint angles of one arm from the key-points seen by V fixed, calibrated cameras
+ * (csrc/kin_views_core.h, host and device code; csrc/kin_views.hip; tests/kinviews_host_check.cpp; tests/kinviews_oracle.py is the
+ * float64 statement).  hrp_kin_solve_views is ONE launch, one 64-lane workgroup per sample, fp64 inside, no atomics and no shuffles.
+ * View v = 0 .. V-1, 1 <= V <= HRP_KIN_MAX_VIEWS, has intrinsics K_v, a fixed camera-from-base pose (w_v, t_v) - angle-axis, then
+ * translation: the cTr of a fixed-camera calibration -, 2-D key-points x_vk and optional weights.  With p = the free joints ascending
+ * it minimises
+ *   C(p) = sum_v sum_k w2d[v,k] |x_vk - pi(K_v, R(w_v) FK_k(q) + t_v)|^2  +  sum_{j free} prior_q[j] (q_j - q0_j)^2
+ * Everything else is hrp_kin_solve's with free_pose = 0 and root = 0, with "the used 2-D points" read as those of all views: the LM
+ * loop, the trial and its clamping, the held joints and the stopping rules; usable points (a view whose points are all NaN or of
+ * weight 0 contributes nothing); rows = 2 (used points over all views) + priors; HRP_KIN_FEW_ROWS, HRP_KIN_BAD_START,
+ * HRP_KIN_AT_LIMIT and HRP_KIN_CONVERGED; a trial is rejected when a used point of ANY view has camera depth <= 0; cov under the same
+ * conditions; fixed joints are copied through bit for bit.  Every sum is taken in a fixed order - views ascending, then
+ * hrp_kin_solve's row order - so two calls return the same bytes.  The forward kinematics runs once per evaluation, whatever V is.
+ * rms is taken over the used points of all views, rms_view [V] over each view's (0 for a view without any): a camera that has moved
+ * since its calibration shows there.  used_view [V]: the used points per view.  xyz / uv: the camera-frame key-points of every view at
+ * the returned joints and their projections.  No host synchronisation, caller-owned buffers: graph-capturable.
+ * Refused (HRP_ERR_ARG, nothing is launched): a null descriptor or required pointer (chain, pts2d, K, poses, and q0, q when dof > 0),
+ * B <= 0, V outside 1 .. HRP_KIN_MAX_VIEWS, nkp outside 1 .. HRP_FK_MAX_KP, dof outside 0 .. HRP_FK_MAX_JOINTS, a free_q bit at or
+ * above dof, K_stride not 0 or 9, pose_stride not 0 or 1, more than 64 KB of LDS (the largest legal sizes need 61 KB). */
+#define HRP_KIN_MAX_VIEWS 8
+typedef struct hrp_kin_views_desc {
+  const hrp_fk_chain* chain;              /* device */
+  const float *pts2d, *w2d;               /* [B,V,nkp,2]; [B,V,nkp] >= 0 or NULL (= 1) */
+  const float* K; int32_t K_stride;       /* [B,V,9] with 9, or [V,9] with 0 = shared over the batch */
+  int32_t nkp;                            /* the chain's nkp */
+  const float* q0;                        /* [B,dof] start and prior mean */
+  const float* poses;                     /* [B,V,6] or [V,6]: (w_v, t_v) camera from base */
+  int32_t pose_stride, V;                 /* 1 = per sample, 0 = shared over the batch */
+  const float *q_lo, *q_hi, *prior_q;     /* [dof] each, optional */
+  uint32_t free_q; int32_t B;
+  int32_t dof, reserved;                  /* the chain's dof */
+  float* q;                               /* [B,dof]: the solution, fixed joints copied through */
+  float *xyz, *uv;                        /* optional [B,V,nkp,3], [B,V,nkp,2] */
+  float *rms, *rms_view;                  /* [B]; [B,V] */
+  int32_t *status, *used_view;            /* [B,4] = (flags, LM trials, rows, npar); [B,V] */
+  float* cov;                             /* optional [B,npar,npar] */
+} hrp_kin_views_desc;
+int hrp_kin_solve_views(const hrp_kin_views_desc* d, void* stream);
 
 /* Kinematic filter: hrp_kin_solve's parameters tracked over frames by an iterated extended Kalman filter in information form, with a
  * constant-velocity prior and an innovation gate (csrc/kin_filter_core.h, host and device code; csrc/kin_filter.hip;

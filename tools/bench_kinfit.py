@@ -17,7 +17,12 @@ Run on the GPU box: ``python tools/bench_kinfit.py [--filter]``; prints one JSON
 per (case, B): the Panda with a fixed camera (n = 6) and holistic (n = 12) filtered over 256 frames of a sinusoidal motion with a
 ring of 256 slots, and a synthetic history with n = 20 on the Baxter's chain; B = 1, 16; per L = 8, 32, 256 and cov on / off the
 microseconds per call and per frame (device events, 5 + 30 calls), next to the filter step's microseconds per frame without and with
-the recording launch (events around the 256 steps of the same run; their difference is ``hrp_kin_history_push``)."""
+the recording launch (events around the 256 steps of the same run; their difference is ``hrp_kin_history_push``).
+
+``--views V[,V...]`` times the multi-view refit instead (``kin_solve_views``, csrc/kin_views.hip) and prints one JSON line per (V, B):
+the same draws of the Panda seen with +-1 px noise from the first V cameras of tests/kinviews_oracle.py (1.5 - 2 m away, looking at
+(0, 0, 0.4)), the six observable joints free, start 0.15 rad off; microseconds per call, the smallest and largest LM trial count of the
+batch and the microseconds per trial of the slowest sample, next to ``kin_solve`` in fixed_camera mode on view 0 alone in the same run."""
 import json
 import os
 import sys
@@ -176,9 +181,40 @@ def smooth_rows():
             print(json.dumps(row), flush=True)
 
 
+def views_rows(views):
+    import kinviews_oracle as kv
+    robot = URDFRobot("panda")
+    tab = ko.tables(robot.chain)
+    poses = np.stack([kv.look_at(c) for c in kv.CAMERAS])
+    Kd = torch.from_numpy(K).to(DEV)
+    for V in views:
+        for B in (1, 16, 64, 1024):
+            _, q, q0, _ = batch(robot, B, 0)
+            rng = np.random.default_rng(1000 + B)
+            x = np.stack([[ko.project(K, ko.keypoints(tab, qb, ko.rodrigues(c[:3]), c[3:], 0)) + rng.uniform(-1, 1, (7, 2)) for c in poses[:V]]
+                          for qb in q.cpu().numpy().astype(np.float64)[:64]])
+            x = torch.from_numpy(np.float32(x[[b % len(x) for b in range(B)]])).to(DEV)
+            multi = kinfit.MultiViewRefit(robot, poses[:V])
+            us, res = timed_us(lambda: multi.solve(x, Kd.expand(V, 3, 3), q0))
+            st = res.status.cpu().numpy()
+            row = dict(V=V, B=B, views_us=round(us, 1), views_trials=[int(st[:, 1].min()), int(st[:, 1].max())],
+                       views_converged=int((st[:, 0] & 1).sum()), views_us_per_trial=round(us / max(int(st[:, 1].max()), 1), 2))
+            single = kinfit.KinematicRefit(robot, "fixed_camera", cTr=poses[0])
+            x0 = x[:, 0].contiguous()
+            us, res = timed_us(lambda: single.solve(x0, Kd, q0))
+            st = res.status.cpu().numpy()
+            row.update(fixed_camera_view0_us=round(us, 1), fixed_camera_view0_trials=[int(st[:, 1].min()), int(st[:, 1].max())],
+                       fixed_camera_view0_us_per_trial=round(us / max(int(st[:, 1].max()), 1), 2))
+            print(json.dumps(row), flush=True)
+
+
 def main():
     if "--smooth" in sys.argv[1:]:
         return smooth_rows()
+    if "--views" in sys.argv[1:]:
+        i = sys.argv.index("--views")
+        views = [int(v) for v in sys.argv[i + 1].split(",")] if i + 1 < len(sys.argv) else [1, 2, 4]
+        return views_rows(views)
     with_filter = "--filter" in sys.argv[1:]
     robot = URDFRobot("panda")
     Kd = torch.from_numpy(K).to(DEV)
